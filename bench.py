@@ -11,10 +11,15 @@ batch = 256*N (2048 at N=8 = the reference's configuration).  Inputs (fp16 laten
 dataloader yields them) are resident in HBM before the timed region; timestep and noise draws are inside it, as in the
 reference's forward.  Weights are torch-default random init (seed 17).
 
-Prints ONE JSON line on rank 0.  `value` comes from an UN-INSTRUMENTED timed loop; `roofline` (the dominant kernel: the
-256x320-tile, 16-wave implicit-GEMM gemm_nt2_kernel<4,5,4,4>, conv / linear forward + dgrad) and `kernels` come from a
-second short loop with HIP events around every launch; `secondary` is the 512-px row of the metric (latents 4x64x64,
-batch 64 per GPU) measured in the same process; `cpu_baseline` is the oracle port on the host cores (N=1 only).
+Prints ONE JSON line on rank 0.  `value` and `ms_per_step` come from an UN-INSTRUMENTED timed loop; a plain run does
+nothing else.  With --full the line also carries: `roofline` (the dominant kernel: the 256x320-tile, 16-wave
+implicit-GEMM gemm_nt2_kernel<4,5,4,4>, conv / linear forward + dgrad) and `kernels` from a second short loop with HIP
+events around every launch; `secondary`, the 512-px row of the metric (latents 4x64x64, batch 64 per GPU) measured in the
+same process; `cpu_baseline`, the oracle port on the host cores (N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed, on rank 0, before anything else runs: `loss.npy` (float64,
+the step's loss) and a fixed sample (DUMP_SAMPLE offsets drawn with seed DUMP_SEED) of the flat fp32 gradient and of
+the updated fp32 master weights (`grad_sample.npy`, `master_sample.npy`, float32, 16 MiB each).
 """
 import argparse
 import json
@@ -36,6 +41,8 @@ PROFILE_STEPS = 2      # instrumented steps behind `roofline` / `kernels` (outsi
 SECONDARY_STEPS = 5    # timed steps of the 512-px secondary block
 PEAK_BF16_TFLOPS = 2500.0  # dense MFMA bf16 peak, /opt/skills/guides/MI355X_MICROARCH.md
 README_8xA100 = {32: 1100.0, 64: 290.0}  # /root/reference README.md:56 (8xA100, global batch 2048)
+DUMP_SAMPLE = 1 << 22  # flat offsets sampled by --dump-outputs (with replacement, sorted)
+DUMP_SEED = 0
 
 
 def _usable_cores():
@@ -128,6 +135,17 @@ def kernel_table(prof):
     return kern, dom, roof, shapes
 
 
+def dump_outputs(out_dir, loss, unet):
+    """--dump-outputs: the last timed step's loss and a seeded sample of its gradient and updated weights, as .npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, unet.master.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(unet.master.device)
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, 'grad_sample.npy'), unet.grad[idx].cpu().numpy())
+    np.save(os.path.join(out_dir, 'master_sample.npy'), unet.master[idx].cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -155,13 +173,20 @@ def main():
     ap.add_argument('--latent', type=int, default=32, help='latent side: 32 (256 px), 64 (512 px), 96 (768 px v-pred)')
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default 256 @32, 64 @64, 16 @96)')
     ap.add_argument('--microbatch', type=int, default=None)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the per-kernel timing loop, the 512-px secondary block and the '
+                         'CPU baseline (each can be left out with its --no-* option)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip the 512-px secondary block')
     ap.add_argument('--full-pipeline', action='store_true',
                     help='BASELINE cfg 3: precomputed_latents=false - frozen VAE-encode + CLIP text-encode on PyTorch-ROCm '
                          '(random-init fp16 encoders, synthetic images / token ids) inside the timed step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s loss, gradient and weight samples to DIR/*.npy')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(a.gpus))
@@ -217,9 +242,11 @@ def main():
 
     # (1) the measured value: no per-kernel instrumentation inside the timed region
     dt, lossv = timed(batch, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:   # before any further step changes the gradient and the weights
+        dump_outputs(a.dump_outputs, lossv, model.unet)
     # (2) per-kernel timings (HIP events around every launch, on the launch stream) from a second, short loop
     prof = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         ops.PROFILE = {}
         for _ in range(PROFILE_STEPS):
             trainer.train_batch(batch)
@@ -227,7 +254,7 @@ def main():
         prof, ops.PROFILE = ops.PROFILE, None
     # (3) the metric is quoted "@256 and @512": the 512-px row (latents 4x64x64, batch 64 per GPU) as a secondary block
     second = None
-    if S == 32 and not a.full_pipeline and not a.no_secondary:
+    if a.full and S == 32 and not a.full_pipeline and not a.no_secondary:
         B2 = 64
         g2 = torch.Generator().manual_seed(2000 + rank)
         batch2 = {'image_latents': torch.randn(B2, 4, 64, 64, generator=g2).half().to(dev),
@@ -302,7 +329,7 @@ def main():
                     print(f'  {str(tag):48s} n={n_:4d} ms={ms_:8.2f} TF/s={fl_ / ms_ / 1e9:7.1f}', file=sys.stderr)
         if second is not None:
             out['secondary'] = second
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

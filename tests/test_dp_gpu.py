@@ -119,8 +119,8 @@ def test_bench_launches_its_own_ranks(dev):
                                                             'HSA_ENABLE_IPC_MODE_LEGACY')}
     env['DA_DIST_BACKEND'] = 'gloo'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--batch', '32', '--steps', '2',
-                        '--warmup', '1', '--no-secondary', '--no-cpu-baseline'], env=env, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+                        '--warmup', '1', '--full', '--no-secondary', '--no-cpu-baseline'], env=env, capture_output=True,
+                       text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
