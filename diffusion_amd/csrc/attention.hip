@@ -674,7 +674,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(AttnParams p
     vf[ks] = kv ? ld8(p.V + ((long)b * p.Nk + key) * p.ldv + c) : zero8();
   }
   // ---- K^T fragments of this wave's 16-column slice (d = 16*wave .. +15) for the dQ product: the K rows go through a plain
-  // [key][64] image once (rows of keys past Nk are zero, so whatever their dS holds adds nothing), read transposed
+  // [key][64] image once (rows of keys past Nk are zero, and so is their dS: see the mask after the softmax arithmetic),
+  // read transposed
   {
     const int krow = tid >> 1, half = tid & 1;  // 32*NW rows x two 64-byte halves
     const bf16* src = p.K + ((long)b * p.Nk + krow) * p.ldk + hd * 64 + half * 32;
@@ -842,6 +843,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(AttnParams p
     }
     bf16x8 pf[2] = {pack8(pr, 0), pack8(pr, 1)};
     bf16x8 dsf[2] = {pack8(s, 0), pack8(s, 1)};
+    // keys past Nk: S = 0, so p = exp2(-L2[q]) is +inf once a row's log2-sum-exp drops below about -127, and the zeroed
+    // K^T row they meet in the dQ product would make 0 * inf = NaN.  Their dS is zeroed here (what the dQ kernel's tail step
+    // does); their P only reaches their own dK / dV columns, which are never stored.  Masking the packed dS compiles to
+    // no more VALU work in the loop than without it (starting S at -inf instead costs 16 VGPRs the kernel does not have).
+    if (!kv) { dsf[0] = zero8(); dsf[1] = zero8(); }
     // dS^T -> LDS for the dQ product after the barrier: registers 4*rg .. 4*rg+3 are queries 8*rg + 4*h .. +3 of this lane's key
     {
       char* drow_p = dsbuf + (t & 1) * FU_DS + key * 64 + 8 * h;

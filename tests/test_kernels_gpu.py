@@ -205,13 +205,16 @@ def test_gemm_nt_persistent_tile_walk(ops, dev, grid):
     check(ref[2], h[:, :inner] * F.gelu(h[:, inner:]), what='persistent geglu')
 
 
-@pytest.mark.parametrize('variant', [12, 10, 11, 14, 5, 4, 18])
-def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant):
+@pytest.mark.parametrize('variant,de', [pytest.param(v, de, id=str(v) if de == 1 else f'{v}-de{de}')
+                                        for de in (1, 2, 3) for v in (12, 10, 11, 14, 5, 4, 18)])
+def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant, de):
     """The direct epilogue (accumulators -> bf16 -> v_permlane16_swap -> 16-byte stores, residual fetched in the same lane
     layout; da_set_option('gemm_nt_de', 1), the default) against the LDS strip epilogue it replaces (0): same sums, same
     roundings, so every form must agree BIT FOR BIT - linears (persistent walk), 3x3 convolutions with the per-image row
     bias and a residual (one tile per workgroup, and the persistent convolution walk at a forced grid), stride 2, its
-    dgrad, the fused upsample, ragged row / column tails, strided views, an in-place residual."""
+    dgrad, the fused upsample, ragged row / column tails, strided views, an in-place residual.  de = 2 / 3 (opt-in) also
+    send the linears without / with a residual through the direct epilogue: 1 leaves them on the strip epilogue on both
+    sides of the comparison."""
     ops.set_option('gemm_nt_variant', variant)
 
     def all_forms():
@@ -266,7 +269,7 @@ def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant):
     try:
         ops.set_option('gemm_nt_de', 0)
         ref = all_forms()
-        ops.set_option('gemm_nt_de', 1)
+        ops.set_option('gemm_nt_de', de)
         got = all_forms()
     finally:
         ops.set_option('gemm_nt_de', 1)
