@@ -40,13 +40,17 @@ SIGNATURES = {
     'da_silu_fwd': [_vp, _l, _vp, _l, _i, _i, _vp],
     'da_gelu_fwd': [_vp, _l, _vp, _l, _i, _i, _vp],
     'da_silu_bwd': [_vp, _l, _vp, _l, _vp, _l, _i, _i, _vp],
+    'da_quick_gelu_fwd': [_vp, _l, _vp, _l, _i, _i, _vp],
     'da_add': [_vp, _l, _vp, _l, _vp, _l, _i, _i, _vp],
     'da_copy2d': [_vp, _l, _vp, _l, _i, _i, _vp],
     'da_upsample2x_fwd': [_vp, _vp, _i, _i, _i, _i, _vp],
     'da_upsample2x_bwd': [_vp, _vp, _i, _i, _i, _i, _vp],
     'da_timestep_embed': [_ll, _vp, _i, _i, _vp],
+    'da_timestep_embed_f32': [_fp, _vp, _i, _i, _vp],
     'da_add_noise': [_fp, _fp, _ll, _fp, _fp, _vp, _fp, _i, _i, _i, _vp],
+    'da_add_noise_ex': [_fp, _fp, _vp, _i, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _vp],
     'da_mse_loss': [_fp, _fp, _vp, _fp, _fp, _l, _f, _f, _i, _vp],
+    'da_mse_loss_c': [_fp, _fp, _vp, _fp, _fp, _l, _i, _f, _f, _i, _vp],
     'da_adamw': [_fp, _fp, _fp, _fp, _vp, _fp, _f, _l, _f, _f, _f, _f, _f, _i, _f, _vp],
     'da_cast_f32_bf16': [_fp, _vp, _l, _vp],
     'da_transpose_weight': [_vp, _vp, _i, _i, _i, _vp],

@@ -73,6 +73,20 @@ __global__ void gelu_fwd_kernel(const bf16* x, long ldx, bf16* y, long ldy, int 
     st8(y + row * ldy + 8 * v, o);
   }
 }
+// ---- quick-GELU x * sigmoid(1.702 x) (CLIP ViT-L/14's MLP activation, hidden_act = "quick_gelu"); forward only
+__global__ void quick_gelu_fwd_kernel(const bf16* x, long ldx, bf16* y, long ldy, int nvec, long total) {
+  GRID_STRIDE(i, total) {
+    long row = i / nvec;
+    int v = (int)(i - row * nvec);
+    bf16x8 a = ld8(x + row * ldx + 8 * v), o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float f = bf2f(a[e]);
+      o[e] = f2bf(f / (1.0f + expf(-1.702f * f)));
+    }
+    st8(y + row * ldy + 8 * v, o);
+  }
+}
 __global__ void silu_bwd_kernel(const bf16* x, long ldx, const bf16* dy, long lddy, bf16* dx, long lddx, int nvec,
                                 long total) {
   GRID_STRIDE(i, total) {
@@ -146,7 +160,9 @@ __global__ void upsample2x_bwd_kernel(const bf16* dy, bf16* dx, int H, int W, in
 }
 
 // ---- sinusoidal timestep embedding: [cos(t f_i) | sin(t f_i)], f_i = 10000^(-i/half)
-__global__ void timestep_embed_kernel(const long long* t, bf16* out, int B, int dim) {
+// T = long long (discrete DDPM steps) or float (continuous time): an integer-valued float t gives the same bits
+template <typename T>
+__global__ void timestep_embed_kernel(const T* t, bf16* out, int B, int dim) {
   const int half = dim >> 1;
   GRID_STRIDE(i, (long)B * half) {
     int b = (int)(i / half), k = (int)(i - (long)b * half);
@@ -180,6 +196,41 @@ __global__ void add_noise_kernel(const float* x0, const float* eps, const long l
   }
 }
 
+// ---- general forward diffusion: C (1..8) channels, discrete (int64 t + sqrt(abar) tables) or continuous (fp32 angle t:
+// cos t x0 + sin t eps) noising; target eps, v or x0.  inputs NCHW fp32 [B,C,HW]; outputs NHWC-8 (pad channels = 0)
+template <bool CONT>
+__global__ void add_noise_ex_kernel(const float* x0, const float* eps, const void* tv, const float* sqrt_ac,
+                                    const float* sqrt_1mac, bf16* xt, float* target, int C, int HW, long total_pix,
+                                    int kind) {
+  GRID_STRIDE(i, total_pix) {
+    long b = i / HW;
+    int pix = (int)(i - b * HW);
+    float a, s;
+    if (CONT) {
+      const float tt = static_cast<const float*>(tv)[b];
+      a = cosf(tt);
+      s = sinf(tt);
+    } else {
+      const long long tt = static_cast<const long long*>(tv)[b];
+      a = sqrt_ac[tt];
+      s = sqrt_1mac[tt];
+    }
+    bf16x8 o = zero8();
+    float tg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        float x = x0[(b * C + c) * HW + pix], n = eps[(b * C + c) * HW + pix];
+        o[c] = f2bf(a * x + s * n);
+        tg[c] = kind == 1 ? (a * n - s * x) : (kind == 2 ? x : n);
+      }
+    }
+    st8(xt + i * 8, o);
+    *reinterpret_cast<f32x4*>(target + i * 8) = f32x4{tg[0], tg[1], tg[2], tg[3]};
+    *reinterpret_cast<f32x4*>(target + i * 8 + 4) = f32x4{tg[4], tg[5], tg[6], tg[7]};
+  }
+}
+
 // ---- MSE loss over the 4 valid channels of NHWC-8 tensors, and its gradient
 __global__ void mse_partial_kernel(const float* pred, const float* target, bf16* dpred, float* partial,
                                    long total_pix, float grad_coef) {
@@ -194,6 +245,35 @@ __global__ void mse_partial_kernel(const float* pred, const float* target, bf16*
       float d = p[c] - q[c];
       acc += d * d;
       g[c] = f2bf(d * grad_coef);
+    }
+    st8(dpred + i * 8, g);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int w = 0; w < PW_BLOCK / 64; ++w) s += sh[w];
+    partial[blockIdx.x] = s;
+  }
+}
+// ---- the same over C (1..8) valid channels; dpred is exactly 0 in the pad channels
+__global__ void mse_partial_c_kernel(const float* pred, const float* target, bf16* dpred, float* partial,
+                                     long total_pix, int C, float grad_coef) {
+  __shared__ float sh[PW_BLOCK / 64];
+  float acc = 0.f;
+  GRID_STRIDE(i, total_pix) {
+    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
+    const f32x4 q0 = *reinterpret_cast<const f32x4*>(target + i * 8),
+                q1 = *reinterpret_cast<const f32x4*>(target + i * 8 + 4);
+    bf16x8 g = zero8();
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        float d = (c < 4 ? p0[c & 3] : p1[c & 3]) - (c < 4 ? q0[c & 3] : q1[c & 3]);
+        acc += d * d;
+        g[c] = f2bf(d * grad_coef);
+      }
     }
     st8(dpred + i * 8, g);
   }
@@ -396,6 +476,16 @@ extern "C" int da_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, in
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
+extern "C" int da_quick_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
+  CHK8(C); CHK8(ldx); CHK8(ldy);
+  long total = (long)M * (C >> 3);
+  hipLaunchKernelGGL(quick_gelu_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, ldx,
+                     (bf16*)y, ldy, C >> 3, total);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
 extern "C" int da_silu_bwd(const void* x, long ldx, const void* dy, long lddy, void* dx, long lddx, int M, int C,
                            hipStream_t s) {
   DA_CLEAR_ERR();
@@ -451,8 +541,16 @@ extern "C" int da_upsample2x_bwd(const void* dy, void* dx, int B, int H, int W, 
 extern "C" int da_timestep_embed(const long long* t, void* out, int B, int dim, hipStream_t s) {
   DA_CLEAR_ERR();
   if (B <= 0 || dim <= 0 || (dim & 1)) return DA_ERR_SHAPE;
-  hipLaunchKernelGGL(timestep_embed_kernel, dim3(pw_blocks((long)B * dim / 2)), dim3(PW_BLOCK), 0, s, t, (bf16*)out,
-                     B, dim);
+  hipLaunchKernelGGL(timestep_embed_kernel<long long>, dim3(pw_blocks((long)B * dim / 2)), dim3(PW_BLOCK), 0, s, t,
+                     (bf16*)out, B, dim);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+extern "C" int da_timestep_embed_f32(const float* t, void* out, int B, int dim, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B <= 0 || dim <= 0 || (dim & 1)) return DA_ERR_SHAPE;
+  hipLaunchKernelGGL(timestep_embed_kernel<float>, dim3(pw_blocks((long)B * dim / 2)), dim3(PW_BLOCK), 0, s, t,
+                     (bf16*)out, B, dim);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -478,6 +576,38 @@ extern "C" int da_mse_loss(const float* pred, const float* target, void* dpred, 
   DA_CHECK_LAUNCH();
   hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss,
                      1.0f / (4.0f * (float)total_pix), weight, accumulate);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+extern "C" int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f32, const float* sqrt_ac,
+                               const float* sqrt_1mac, void* xt, float* target, int B, int C, int HW, int target_kind,
+                               hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B <= 0 || HW <= 0 || C < 1 || C > 8 || target_kind < 0 || target_kind > 2 || !t) return DA_ERR_SHAPE;
+  if (!t_is_f32 && (!sqrt_ac || !sqrt_1mac)) return DA_ERR_SHAPE;
+  if (((uintptr_t)xt & 15) || ((uintptr_t)target & 15)) return DA_ERR_SHAPE;
+  long total = (long)B * HW;
+  if (t_is_f32)
+    hipLaunchKernelGGL(add_noise_ex_kernel<true>, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, x0, eps, t, sqrt_ac,
+                       sqrt_1mac, (bf16*)xt, target, C, HW, total, target_kind);
+  else
+    hipLaunchKernelGGL(add_noise_ex_kernel<false>, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, x0, eps, t, sqrt_ac,
+                       sqrt_1mac, (bf16*)xt, target, C, HW, total, target_kind);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+extern "C" int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
+                             long total_pix, int C, float grad_coef, float weight, int accumulate, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (total_pix <= 0 || C < 1 || C > 8) return DA_ERR_SHAPE;
+  if ((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) & 15)) return DA_ERR_SHAPE;
+  int blocks = pw_blocks(total_pix);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(mse_partial_c_kernel, dim3(blocks), dim3(PW_BLOCK), 0, s, pred, target, (bf16*)dpred, scratch,
+                     total_pix, C, grad_coef);
+  DA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss,
+                     (float)(1.0 / ((double)C * (double)total_pix)), weight, accumulate);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

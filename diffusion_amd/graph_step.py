@@ -85,8 +85,10 @@ class GraphStepCache:
         self.graphs: Dict[Tuple, GraphedMicrobatch] = {}
 
     def usable(self, batch) -> bool:
+        """Only latent-space models with precomputed latents are captured: a model without them (PixelDiffusion encodes
+        its captions every step and has no latent keys) runs eagerly."""
         m = self.model
-        return (ops.PROFILE is None and m.precomputed_latents and m.image_latents_key in batch
+        return (ops.PROFILE is None and getattr(m, 'precomputed_latents', False) and m.image_latents_key in batch
                 and m.text_latents_key in batch and m.loss_fn is torch.nn.functional.mse_loss)
 
     def step(self, batch, weight: float):

@@ -1,4 +1,4 @@
-"""Constructors for diffusion models - mirrors /root/reference diffusion/models/models.py:28-112.
+"""Constructors for diffusion models - mirrors the reference's diffusion/models/models.py:28-228.
 
 ``stable_diffusion_2`` keeps the reference signature (:28-39).  Differences forced by the platform:
   * nothing is fetched: the SD-2-base / SD-2.1 U-Net configs are embedded (``unet.UNetConfig``); ``model_name`` may
@@ -7,7 +7,12 @@
   * the U-Net is ``UNetHIP`` (hand-written gfx950 kernels) instead of ``diffusers.UNet2DConditionModel``;
   * the frozen VAE / text encoder are stock PyTorch-ROCm modules (random-init without local weights) and are only
     built when they can be needed (``precomputed_latents=False``) or when asked for with ``build_encoders=True``;
-  * xformers (:109-111) is not a concept here: attention is always the fused flash kernels."""
+  * xformers (:109-111) is not a concept here: attention is always the fused flash kernels.
+
+``discrete_pixel_diffusion`` / ``continuous_pixel_diffusion`` keep the reference signatures (:115, :175-179); the same
+platform rules apply: the CLIP ViT-L/14 text config is embedded and ``clip_model_name`` may be a local directory with
+its weights and tokenizer files (loaded strictly), else the encoder is random-init.  The frozen encoder runs on the HIP
+kernels (``TextEncoderHIP``)."""
 from __future__ import annotations
 
 import os
@@ -17,6 +22,8 @@ from typing import List, Optional
 import torch
 
 from .composer_shim import MeanSquaredError
+from ..schedulers.schedulers import ContinuousTimeScheduler
+from .pixel_diffusion import PixelDiffusion
 from .schedulers import DDIMScheduler, DDPMScheduler
 from .stable_diffusion import StableDiffusion
 from .unet import UNetConfig, UNetHIP
@@ -166,4 +173,65 @@ def stable_diffusion_2(
     )
     model.vae_hip = vae_hip if build_encoders else None
     model.text_hip = text_hip if build_encoders else None
+    return model
+
+
+def _pixel_text_encoder(clip_model_name: str, hidden_size: int):
+    """CLIP ViT-L/14 text encoder + tokenizer (reference models.py:136-137, :197-198), frozen, on the HIP kernels."""
+    from .text import build_clip_text_encoder, build_tokenizer
+    from .text_hip import TextEncoderHIP
+    local = clip_model_name if os.path.isdir(clip_model_name) else None
+    if local is None:
+        warnings.warn(f'{clip_model_name!r} is not a local directory: the CLIP text encoder is RANDOM-INIT (nothing is '
+                      'fetched); fine for throughput runs and tests, meaningless for real training')
+        text_encoder = build_clip_text_encoder(None, hidden_size=hidden_size, intermediate_size=4 * hidden_size,
+                                               num_attention_heads=max(1, hidden_size // 64))
+    else:
+        text_encoder = build_clip_text_encoder(local)
+    text_encoder = text_encoder.to('cuda').requires_grad_(False)
+    return text_encoder, build_tokenizer(local), TextEncoderHIP(text_encoder)
+
+
+def _pixel_unet(unet_config: Optional[UNetConfig], seed: int) -> UNetHIP:
+    # reference: UNet2DConditionModel(in_channels=3, out_channels=3, attention_head_dim=[5, 10, 20, 20],
+    # cross_attention_dim=768, flip_sin_to_cos=True, use_linear_projection=True), random-init
+    return UNetHIP(unet_config or UNetConfig.pixel(), device='cuda', seed=seed, init=True)
+
+
+def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
+                             unet_config: Optional[UNetConfig] = None, seed: int = 17):
+    """Discrete-time (DDPM, 1000 steps) pixel diffusion; DDIM for inference (reference models.py:115-172)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('discrete_pixel_diffusion: an MI355X is required (the U-Net has no CPU path)')
+    unet = _pixel_unet(unet_config, seed)
+    text_encoder, tokenizer, text_hip = _pixel_text_encoder(clip_model_name, unet.cfg.cross_attention_dim)
+    noise_scheduler = DDPMScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
+                                    beta_schedule='scaled_linear', prediction_type=prediction_type, clip_sample=False)
+    inference_scheduler = DDIMScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
+                                        beta_schedule='scaled_linear', clip_sample=False, steps_offset=1,
+                                        prediction_type=prediction_type)
+    model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
+                           prediction_type=prediction_type, train_metrics=[MeanSquaredError()],
+                           val_metrics=[MeanSquaredError()])
+    model.text_hip = text_hip
+    return model
+
+
+def continuous_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
+                               use_ode=False, train_t_max=1.570795, inference_t_max=1.56,
+                               unet_config: Optional[UNetConfig] = None, seed: int = 17):
+    """Continuous-time pixel diffusion: the VP process with angle = time (tangent schedule), t in [0, train_t_max) for
+    training, the reverse SDE (or with ``use_ode`` the probability-flow ODE) from ``inference_t_max`` for generation
+    (reference models.py:175-228)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('continuous_pixel_diffusion: an MI355X is required (the U-Net has no CPU path)')
+    unet = _pixel_unet(unet_config, seed)
+    text_encoder, tokenizer, text_hip = _pixel_text_encoder(clip_model_name, unet.cfg.cross_attention_dim)
+    noise_scheduler = ContinuousTimeScheduler(t_max=train_t_max, prediction_type=prediction_type)
+    inference_scheduler = ContinuousTimeScheduler(t_max=inference_t_max, prediction_type=prediction_type,
+                                                  use_ode=use_ode)
+    model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
+                           prediction_type=prediction_type, continuous_time=True, train_metrics=[MeanSquaredError()],
+                           val_metrics=[MeanSquaredError()])
+    model.text_hip = text_hip
     return model

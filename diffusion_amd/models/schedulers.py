@@ -3,7 +3,8 @@
 ``DDPMScheduler`` stands where diffusion/models/models.py:88 loads ``diffusers.DDPMScheduler`` (hyper-parameters
 restated in-tree at models.py:134-145); the reference touches ``len(scheduler)`` (stable_diffusion.py:177),
 ``add_noise`` (:180) and ``num_train_timesteps`` (:235).  ``get_velocity`` follows the use at
-diffusion/models/pixel_diffusion.py:90-91.  ``DDIMScheduler`` (models.py:89) carries what ``generate()`` needs
+diffusion/models/pixel_diffusion.py:90-91; ``prediction_type='sample'`` (x0 prediction, :86-87) is the third target the
+pixel models train on.  ``DDIMScheduler`` (models.py:89) carries what ``generate()`` needs
 (stable_diffusion.py:354-375): ``set_timesteps``, ``timesteps``, ``init_noise_sigma``, ``scale_model_input``, ``step``.
 """
 from __future__ import annotations
@@ -78,6 +79,9 @@ class DDIMScheduler(DDPMScheduler):
         if self.prediction_type == 'v_prediction':
             x0 = ac_t.sqrt() * sample - (1 - ac_t).sqrt() * model_output
             eps = ac_t.sqrt() * model_output + (1 - ac_t).sqrt() * sample
+        elif self.prediction_type == 'sample':   # the pixel models' x0 prediction (pixel_diffusion.py:86-87)
+            x0 = model_output
+            eps = (sample - ac_t.sqrt() * x0) / (1 - ac_t).sqrt()
         else:
             eps = model_output
             x0 = (sample - (1 - ac_t).sqrt() * eps) / ac_t.sqrt()

@@ -1,4 +1,4 @@
-"""Frozen OpenCLIP-H text encoder + tokenizer on stock PyTorch-ROCm / transformers (no hub access).
+"""Frozen OpenCLIP-H (SD-2) / CLIP ViT-L/14 (pixel models) text encoders + tokenizer on stock PyTorch-ROCm / transformers (no hub access).
 
 Stands where diffusion/models/models.py:82,85,87 load ``CLIPTextModel`` / ``CLIPTokenizer`` by hub NAME.  Here the
 SD-2 text-encoder config is embedded (hidden 1024, 23 layers, 16 heads, 77 positions, vocab 49408 - the published
@@ -23,6 +23,28 @@ def build_text_encoder(local_dir: Optional[str] = None, dtype=torch.float32, num
                          max_position_embeddings=77, hidden_act='gelu', projection_dim=512, pad_token_id=1,
                          bos_token_id=0, eos_token_id=2)
     return CLIPTextModel(cfg).to(dtype)
+
+
+# openai/clip-vit-large-patch14's published text configuration (the encoder of the pixel models, reference
+# models.py:136,197 load it by hub name): 768 hidden, 12 layers, 12 heads, 3072 intermediate, quick_gelu, eps 1e-5
+CLIP_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
+                     max_position_embeddings=77, hidden_act='quick_gelu', layer_norm_eps=1e-5, projection_dim=768,
+                     pad_token_id=1, bos_token_id=0, eos_token_id=2)
+
+
+def build_clip_text_encoder(local_dir: Optional[str] = None, dtype=torch.float32, **overrides):
+    """CLIP ViT-L/14 text encoder: strictly loaded from ``local_dir`` when it is a directory (every weight must be
+    present), else random-init on the embedded configuration (``overrides`` narrow it for tests).  Never fetches."""
+    from transformers import CLIPTextConfig, CLIPTextModel
+    if local_dir and os.path.isdir(local_dir):
+        model, info = CLIPTextModel.from_pretrained(local_dir, torch_dtype=dtype, local_files_only=True,
+                                                    output_loading_info=True)
+        missing = [k for k in info.get('missing_keys', []) if 'position_ids' not in k]
+        if missing or info.get('mismatched_keys'):
+            raise RuntimeError(f'{local_dir}: incomplete CLIP text encoder weights (missing {missing[:5]}, '
+                               f'mismatched {info.get("mismatched_keys", [])[:5]})')
+        return model
+    return CLIPTextModel(CLIPTextConfig(**dict(CLIP_L14_TEXT, **overrides))).to(dtype)
 
 
 class ByteTokenizer:

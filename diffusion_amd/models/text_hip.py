@@ -8,7 +8,7 @@ fc1, GELU, fc2 + residual - i.e. the op set the U-Net's transformer blocks alrea
 ``da_gemm_nt`` (bias / residual epilogues).  This module walks the weights of the torch module through those kernels
 (bf16 activations, fp32 accumulation / statistics), the causal self-attention through ``da_attn_fwd_causal`` (the flash
 forward kernel with a per-query key limit; heads are 64-column slices of the fused q|k|v buffer, so nothing is transposed)
-and the MLP activation through ``da_gelu_fwd``.  Only the embedding gather is a torch op.
+and the MLP activation through ``da_gelu_fwd`` (``da_quick_gelu_fwd`` for CLIP ViT-L/14, the pixel models' encoder).  Only the embedding gather is a torch op.
 tests/test_text_hip_gpu.py bounds the difference of the last hidden state against the fp32 torch module.
 """
 from __future__ import annotations
@@ -100,7 +100,7 @@ class TextEncoderHIP:
             if self.act == 'gelu':
                 ops.gelu_fwd(f, f)
             else:
-                f = f * torch.sigmoid(1.702 * f)
+                ops.quick_gelu_fwd(f, f)
             h = self._lin(f, ly['w2'], ly['b2'], residual=h)
         y = self._ln(h, self.lnf, stats)
         return (y.view(B, T, C).float(),)

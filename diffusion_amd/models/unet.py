@@ -54,12 +54,18 @@ class UNetConfig:
         return cls(sample_size=96, prediction_type='v_prediction')
 
     @classmethod
+    def pixel(cls):
+        """The pixel-space U-Net of discrete_ / continuous_pixel_diffusion (reference models.py:124-129 and :188-193): SD-2
+        widths and heads on 3 RGB channels in and out, cross-attention over CLIP ViT-L/14's 768-wide hidden states."""
+        return cls(in_channels=3, out_channels=3, cross_attention_dim=768)
+
+    @classmethod
     def tiny(cls):
         return cls(block_out_channels=(64, 128, 256, 256), attention_head_dim=(1, 2, 4, 4), cross_attention_dim=128)
 
     def validate(self):
-        if self.in_channels != 4 or self.out_channels != 4:
-            raise ValueError('kernels assume 4 latent channels (padded to 8)')
+        if not (1 <= self.in_channels <= 8 and 1 <= self.out_channels <= 8):
+            raise ValueError('kernels take 1..8 input / output channels (padded to 8)')
         if len(self.block_out_channels) != 4 or self.layers_per_block != 2:
             raise ValueError('SD-2 topology: 4 levels, 2 layers per block')
         for c, h in zip(self.block_out_channels, self.attention_head_dim):
@@ -669,8 +675,9 @@ class UNetHIP(nn.Module):
     # whole network
     # ------------------------------------------------------------------------------------------
     def forward_features(self, xt8: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, B: int, S: int):
-        """xt8: [B*S*S, 8] bf16 NHWC(8) noised latents; t: [B] int64; ctx: [B*77, ctx_dim] bf16.
-        Returns pred [B*S*S, 8] fp32 (channels 4..7 are zero) and records everything backward needs."""
+        """xt8: [B*S*S, 8] bf16 NHWC(8) noised inputs; t: [B] int64 (discrete steps) or fp32 (continuous time);
+        ctx: [B*77, ctx_dim] bf16.  Returns pred [B*S*S, 8] fp32 (channels out_channels..7 are zero) and records
+        everything backward needs."""
         cfg = self.cfg
         boc = cfg.block_out_channels
         n = len(boc)
@@ -679,7 +686,10 @@ class UNetHIP(nn.Module):
         tape: List[Tuple[str, tuple]] = []
         # ---- timestep embedding MLP + all 22 time_emb_proj in one GEMM
         te0 = self._bf(B, boc[0])
-        ops.timestep_embed(t, te0)
+        if t.dtype == F32:
+            ops.timestep_embed_f32(t, te0)
+        else:
+            ops.timestep_embed(t, te0)
         te1 = self._lin_fwd(te0, 'time_embedding.linear_1')
         te1s = self._bf(B, cfg.time_embed_dim)
         ops.silu_fwd(te1, te1s)
@@ -878,7 +888,7 @@ class UNetHIP(nn.Module):
     # diffusers-compatible inference call: unet(sample, timestep, encoder_hidden_states)
     # ------------------------------------------------------------------------------------------
     def to_nhwc8(self, x: torch.Tensor) -> torch.Tensor:
-        """[B,4,S,S] any float dtype -> [B*S*S, 8] bf16 (pure relayout; used for the un-noised inference path)."""
+        """[B,C,S,S] (C <= 8) any float dtype -> [B*S*S, 8] bf16 (pure relayout; used for the un-noised inference path)."""
         B, C, H, W = x.shape
         out = torch.zeros(B * H * W, 8, device=self.device_, dtype=BF16)
         out.view(B, H, W, 8)[..., :C] = x.permute(0, 2, 3, 1)
@@ -895,11 +905,14 @@ class UNetHIP(nn.Module):
         B, C, H, W = sample.shape
         if H != W:
             raise ValueError('square latents only')
+        if C != self.cfg.in_channels:
+            raise ValueError(f'sample has {C} channels, the U-Net takes {self.cfg.in_channels}')
         t = torch.as_tensor(timestep, device=self.device_)
         if t.dim() == 0:
             t = t.expand(B)
-        t = t.to(torch.int64).contiguous()
+        # floating timesteps (continuous time: numpy / Python floats, float tensors) stay floats, embedded unrounded
+        t = t.to(F32 if t.is_floating_point() else torch.int64).contiguous()
         pred = self.forward_features(self.to_nhwc8(sample), t, self.prepare_ctx(encoder_hidden_states), B, H)
         self._tape = None
-        out = pred.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2)
+        out = pred.view(B, H, W, 8)[..., :self.cfg.out_channels].permute(0, 3, 1, 2)
         return UNetOutput(sample=out)

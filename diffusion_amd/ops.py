@@ -365,6 +365,14 @@ def gelu_fwd(x, y):
     _lib.call('da_gelu_fwd', a, lda, b, ldb, x.shape[0], x.shape[1], _stream())
 
 
+def quick_gelu_fwd(x, y):
+    a, lda = _mat(x, BF16)
+    b, ldb = _mat(y, BF16)
+    if x.shape != y.shape:
+        raise ValueError('quick_gelu_fwd: shape mismatch')
+    _lib.call('da_quick_gelu_fwd', a, lda, b, ldb, x.shape[0], x.shape[1], _stream())
+
+
 def silu_bwd(x, dy, dx):
     a, lda = _mat(x, BF16)
     b, ldb = _mat(dy, BF16)
@@ -409,6 +417,48 @@ def timestep_embed(t, out):
     _lib.call('da_timestep_embed', t.data_ptr(), out.data_ptr(), t.numel(), out.shape[1], _stream())
 
 
+def timestep_embed_f32(t, out):
+    if t.dtype != F32 or not t.is_cuda or not t.is_contiguous() or out.dtype != BF16 or not out.is_cuda \
+            or not out.is_contiguous() or out.shape[0] != t.numel():
+        raise ValueError('timestep_embed_f32: t fp32 [B] on device, out bf16 [B, dim] on device, both contiguous')
+    _lib.call('da_timestep_embed_f32', t.data_ptr(), out.data_ptr(), t.numel(), out.shape[1], _stream())
+
+
+# target kinds of da_add_noise_ex, by the reference's prediction_type names
+NOISE_TARGETS = {'epsilon': 0, 'v_prediction': 1, 'sample': 2}
+
+
+def add_noise_ex(x0, eps, t, xt, target, prediction_type='epsilon', sqrt_ac=None, sqrt_1mac=None):
+    """Pixel-space noising (C = 1..8 channels): int64 ``t`` with the DDPM tables, or fp32 ``t`` (angles) with the tangent
+    schedule computed in the kernel.  x0 / eps NCHW fp32; xt [B*H*W, 8] bf16 and target [B*H*W, 8] fp32."""
+    if x0.dim() != 4:
+        raise ValueError('add_noise_ex: x0/eps must be [B,C,H,W]')
+    B, C = x0.shape[0], x0.shape[1]
+    HW = x0.shape[2] * x0.shape[3]
+    for z in (x0, eps):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or z.shape != x0.shape:
+            raise ValueError('add_noise_ex: x0/eps must be contiguous fp32 [B,C,H,W] device tensors')
+    if not 1 <= C <= 8:
+        raise ValueError(f'add_noise_ex: {C} channels (1..8 supported)')
+    for z, dt in ((xt, BF16), (target, F32)):
+        if z.dtype != dt or not z.is_cuda or not z.is_contiguous() or z.numel() != B * HW * 8 or z.data_ptr() % 16:
+            raise ValueError('add_noise_ex: xt bf16 [B*HW,8], target fp32 [B*HW,8], contiguous on device')
+    if not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+        raise ValueError('add_noise_ex: t must be a contiguous [B] device tensor')
+    if prediction_type not in NOISE_TARGETS:
+        raise ValueError(f'add_noise_ex: unknown prediction_type {prediction_type!r}')
+    if t.dtype == F32:
+        is_f32, pa, pb = 1, None, None
+    elif t.dtype == torch.int64:
+        if sqrt_ac is None or sqrt_1mac is None or int(sqrt_ac.numel()) != int(sqrt_1mac.numel()):
+            raise ValueError('add_noise_ex: discrete t needs both sqrt(abar) tables')
+        is_f32, pa, pb = 0, _vec(sqrt_ac, sqrt_ac.numel(), 'sqrt_ac'), _vec(sqrt_1mac, sqrt_1mac.numel(), 'sqrt_1mac')
+    else:
+        raise ValueError(f'add_noise_ex: t must be int64 (discrete) or fp32 (continuous), got {t.dtype}')
+    _lib.call('da_add_noise_ex', x0.data_ptr(), eps.data_ptr(), t.data_ptr(), is_f32, pa, pb, xt.data_ptr(),
+              target.data_ptr(), B, C, HW, NOISE_TARGETS[prediction_type], _stream())
+
+
 def add_noise(x0, eps, t, sqrt_ac, sqrt_1mac, xt, target, v_pred):
     B = x0.shape[0]
     HW = x0.shape[2] * x0.shape[3]
@@ -430,6 +480,17 @@ def mse_loss(pred, target, dpred, loss, scratch, total_pix, grad_coef, weight, a
         raise ValueError('mse_loss: sizes')
     _lib.call('da_mse_loss', pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), loss.data_ptr(),
               _f32buf(scratch, 1024), total_pix, float(grad_coef), float(weight), int(accumulate), _stream())
+
+
+def mse_loss_c(pred, target, dpred, loss, scratch, total_pix, C, grad_coef, weight, accumulate):
+    """``mse_loss`` over the first C (1..8) channels of NHWC(8) tensors; dpred is 0 in the pad channels."""
+    for z, dt in ((pred, F32), (target, F32), (dpred, BF16)):
+        if z.dtype != dt or not z.is_cuda or not z.is_contiguous() or z.numel() != total_pix * 8 or z.data_ptr() % 16:
+            raise ValueError('mse_loss_c: pred / target fp32 and dpred bf16, contiguous [total_pix, 8] on device')
+    if loss.dtype != F32 or not loss.is_cuda or not 1 <= int(C) <= 8:
+        raise ValueError('mse_loss_c: loss fp32 on device, 1 <= C <= 8')
+    _lib.call('da_mse_loss_c', pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), loss.data_ptr(),
+              _f32buf(scratch, 1024), total_pix, int(C), float(grad_coef), float(weight), int(accumulate), _stream())
 
 
 def adamw(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale, ema=None, ema_smoothing=0.0):

@@ -207,8 +207,11 @@ class Trainer:
         self.global_batch_size = n * self.world
         mb = self.microbatch
         if mb is None:
-            lat = batch.get(model.image_latents_key) if model.precomputed_latents else batch.get(model.image_key)
-            side = 32 if lat is None else (lat.shape[-1] if model.precomputed_latents else lat.shape[-1] // 8)
+            if hasattr(model, 'unet_input_side'):   # the model knows its U-Net input (pixel models: no VAE, no /8)
+                side = model.unet_input_side(batch)
+            else:
+                lat = batch.get(model.image_latents_key) if model.precomputed_latents else batch.get(model.image_key)
+                side = 32 if lat is None else (lat.shape[-1] if model.precomputed_latents else lat.shape[-1] // 8)
             mb = self.auto_microbatch(n, side)
         starts = list(range(0, n, mb))
         # the first backward of the step WRITES the flat gradient (no zero fill, no read half of the read-add-writes); a

@@ -176,6 +176,9 @@ int da_silu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, da_str
 int da_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, da_stream_t stream);
 int da_silu_bwd(const void* x, long ldx, const void* dy, long lddy, void* dx, long lddx, int M, int C,
                 da_stream_t stream);
+/* quick-GELU x * sigmoid(1.702 x) (CLIP ViT-L/14 text encoder, CLIPTextConfig.hidden_act = "quick_gelu": the encoder
+ * the pixel models build at diffusion/models/models.py:136,197); forward only, may run in place (y == x) */
+int da_quick_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, da_stream_t stream);
 
 /* strided add / copy: residual gradient sums and torch.cat([h, skip], dim=1) of the up blocks */
 int da_add(const void* a, long lda, const void* b, long ldb, void* o, long ldo, int M, int C, da_stream_t stream);
@@ -187,6 +190,9 @@ int da_upsample2x_bwd(const void* dy, void* dx, int B, int H, int W, int C, da_s
 
 /* diffusers Timesteps(flip_sin_to_cos=True, freq_shift=0): out[B][dim] = [cos | sin] (bf16); t is int64 */
 int da_timestep_embed(const long long* t, void* out, int B, int dim, da_stream_t stream);
+/* the same on fp32 t (continuous-time pixel diffusion, t in [0, pi/2): pixel_diffusion.py:78 draws t_max * rand, and
+ * the U-Net embeds the angle unrounded).  Integer-valued t gives the same bits as da_timestep_embed. */
+int da_timestep_embed_f32(const float* t, void* out, int B, int dim, da_stream_t stream);
 
 /* DDPMScheduler.add_noise (stable_diffusion.py:180) fused with the NCHW fp32 -> NHWC(8) bf16 relayout and
  * the training target (eps, or get_velocity when v_pred - pixel_diffusion.py:90-91).
@@ -194,10 +200,27 @@ int da_timestep_embed(const long long* t, void* out, int B, int dim, da_stream_t
 int da_add_noise(const float* x0, const float* eps, const long long* t, const float* sqrt_ac,
                  const float* sqrt_1mac, void* xt, float* target, int B, int HW, int v_pred, da_stream_t stream);
 
+/* The pixel-space noising of pixel_diffusion.py:81-93 (scheduler.add_noise + the target of prediction_type) fused with the
+ * relayout, for C = 1..8 channels.  x0, eps: [B][C][HW] fp32; xt: [B*HW][8] bf16 (channels C..7 zero); target:
+ * [B*HW][8] fp32 (channels C..7 zero); xt and target 16-byte aligned.
+ *   t_is_f32 = 0: t is int64 [B], sqrt_ac / sqrt_1mac the DDPM tables (DDPMScheduler.add_noise / get_velocity);
+ *   t_is_f32 = 1: t is fp32 [B] angles, the tangent schedule of schedulers.py:10-24 / :64-79 in the kernel:
+ *                 x_t = cos t x0 + sin t eps, v = -sin t x0 + cos t eps; the tables are not read (may be NULL).
+ * target_kind: 0 eps, 1 v (v_prediction), 2 x0 (sample).  For C = 4, t_is_f32 = 0 and target_kind 0 / 1 the result is
+ * bit-identical to da_add_noise.  DA_ERR_SHAPE for C outside 1..8, an unknown target_kind or missing tables. */
+int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f32, const float* sqrt_ac,
+                    const float* sqrt_1mac, void* xt, float* target, int B, int C, int HW, int target_kind,
+                    da_stream_t stream);
+
 /* F.mse_loss(pred, target) (stable_diffusion.py:187) over the 4 valid channels of NHWC(8) fp32 tensors and its
  * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats */
 int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
                 float grad_coef, float weight, int accumulate, da_stream_t stream);
+/* the da_mse_loss contract over C = 1..8 valid channels (the 3-channel pixel models' F.mse_loss, pixel_diffusion.py:98):
+ * the mean is over total_pix * C values; dpred is exactly 0 in channels C..7, so the padded conv_out rows get a zero
+ * gradient.  pred, target, dpred 16-byte aligned; DA_ERR_SHAPE for C outside 1..8. */
+int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
+                  int C, float grad_coef, float weight, int accumulate, da_stream_t stream);
 
 /* torch.optim.AdamW step (train.py:33; SD-2-base-256.yaml:55-58) on flat fp32 master/moment buffers, gradient
  * pre-scaled by grad_scale; also writes the bf16 compute shadow.  If ema != NULL the exponential moving average of
