@@ -31,6 +31,7 @@ SIGNATURES = {
     'da_groupnorm_fwd': [_vp, _l, _vp, _l, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _f, _i, _vp],
     'da_groupnorm_bwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i,
                          _vp],
+    'da_groupnorm_plan_for': [_i, _i, _i, _i, _l, _l, _i, C.POINTER(_i)],
     'da_layernorm_fwd': [_vp, _l, _vp, _l, _fp, _fp, _fp, _i, _i, _f, _vp],
     'da_layernorm_bwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _fp, _fp, _fp, _fp, _i, _i, _vp],
     'da_colsum_accum': [_vp, _l, _fp, _fp, _i, _i, _vp],

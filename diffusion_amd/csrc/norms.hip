@@ -1192,30 +1192,43 @@ int launch_gn_res_bwd(const GnResParams& p, int B, hipStream_t stream) {
   return p.silu ? launch_gn_res_bwd2<NL, true, T>(p, B, stream) : launch_gn_res_bwd2<NL, false, T>(p, B, stream);
 }
 
+// the NL instantiation that runs nl data vectors per thread: the smallest compiled one >= nl (da_groupnorm_plan_for reports it)
+int gn_res_nl_inst(int nl, bool bwd, int threads) {
+  if (bwd && threads == 768) return nl <= 11 ? 11 : 14;
+  static const int fwd[] = {1, 2, 3, 4, 6, 8, 11, 16, 21}, bwd1024[] = {1, 2, 3, 4, 6, 8, 11};
+  const int* v = bwd ? bwd1024 : fwd;
+  const int n = bwd ? 7 : 9;
+  for (int i = 0; i < n - 1; ++i)
+    if (nl <= v[i]) return v[i];
+  return v[n - 1];
+}
+
 int dispatch_gn_res_fwd(int nl, const GnResParams& p, int B, hipStream_t s) {
-  if (nl <= 1) return launch_gn_res_fwd<1>(p, B, s);
-  if (nl <= 2) return launch_gn_res_fwd<2>(p, B, s);
-  if (nl <= 3) return launch_gn_res_fwd<3>(p, B, s);
-  if (nl <= 4) return launch_gn_res_fwd<4>(p, B, s);
-  if (nl <= 6) return launch_gn_res_fwd<6>(p, B, s);
-  if (nl <= 8) return launch_gn_res_fwd<8>(p, B, s);
-  if (nl <= 11) return launch_gn_res_fwd<11>(p, B, s);
-  if (nl <= 16) return launch_gn_res_fwd<16>(p, B, s);
-  return launch_gn_res_fwd<21>(p, B, s);
+  switch (gn_res_nl_inst(nl, false, 1024)) {
+    case 1: return launch_gn_res_fwd<1>(p, B, s);
+    case 2: return launch_gn_res_fwd<2>(p, B, s);
+    case 3: return launch_gn_res_fwd<3>(p, B, s);
+    case 4: return launch_gn_res_fwd<4>(p, B, s);
+    case 6: return launch_gn_res_fwd<6>(p, B, s);
+    case 8: return launch_gn_res_fwd<8>(p, B, s);
+    case 11: return launch_gn_res_fwd<11>(p, B, s);
+    case 16: return launch_gn_res_fwd<16>(p, B, s);
+    default: return launch_gn_res_fwd<21>(p, B, s);
+  }
 }
 
 int dispatch_gn_res_bwd(int nl, int threads, const GnResParams& p, int B, hipStream_t s) {
-  if (threads == 768) {
-    if (nl <= 11) return launch_gn_res_bwd<11, 768>(p, B, s);
-    return launch_gn_res_bwd<14, 768>(p, B, s);
+  if (threads == 768) return gn_res_nl_inst(nl, true, 768) == 11 ? launch_gn_res_bwd<11, 768>(p, B, s)
+                                                                  : launch_gn_res_bwd<14, 768>(p, B, s);
+  switch (gn_res_nl_inst(nl, true, 1024)) {
+    case 1: return launch_gn_res_bwd<1, 1024>(p, B, s);
+    case 2: return launch_gn_res_bwd<2, 1024>(p, B, s);
+    case 3: return launch_gn_res_bwd<3, 1024>(p, B, s);
+    case 4: return launch_gn_res_bwd<4, 1024>(p, B, s);
+    case 6: return launch_gn_res_bwd<6, 1024>(p, B, s);
+    case 8: return launch_gn_res_bwd<8, 1024>(p, B, s);
+    default: return launch_gn_res_bwd<11, 1024>(p, B, s);
   }
-  if (nl <= 1) return launch_gn_res_bwd<1, 1024>(p, B, s);
-  if (nl <= 2) return launch_gn_res_bwd<2, 1024>(p, B, s);
-  if (nl <= 3) return launch_gn_res_bwd<3, 1024>(p, B, s);
-  if (nl <= 4) return launch_gn_res_bwd<4, 1024>(p, B, s);
-  if (nl <= 6) return launch_gn_res_bwd<6, 1024>(p, B, s);
-  if (nl <= 8) return launch_gn_res_bwd<8, 1024>(p, B, s);
-  return launch_gn_res_bwd<11, 1024>(p, B, s);
 }
 
 }  // namespace
@@ -1225,6 +1238,20 @@ extern "C" long da_norm_scratch_floats(int B, int HW, int C) {
   long a = (long)B * pick_chunks(B, HW) * C * 2;
   long b = 1024L * C * 2;  // LayerNorm backward: <= 1024 partial rows; colsum: <= 256
   return a > b ? a : b;
+}
+
+extern "C" int da_groupnorm_plan_for(int B, int HW, int C, int G, long ld_min, long ld_max, int bwd, int* out) {
+  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 7) || (ld_min & 7) || (ld_max & 7) || !out) return -1;
+  GnResParams r = {};
+  int nl = 0, threads = 0;
+  if (g_gn_resident && gn_res_plan(B, HW, C, G, ld_min, ld_max, bwd != 0, r, nl, threads)) {
+    const int o[7] = {threads, gn_res_nl_inst(nl, bwd != 0, threads), r.CW, r.parts, r.peers8, r.P, 0};
+    for (int i = 0; i < 7; ++i) out[i] = o[i];
+    return 1;
+  }
+  const int o[7] = {0, 0, C, 1, 0, 0, pick_chunks(B, HW)};
+  for (int i = 0; i < 7; ++i) out[i] = o[i];
+  return 0;
 }
 
 extern "C" int da_groupnorm_fwd(const void* X, long ldx, void* Y, long ldy, const float* gamma, const float* beta,

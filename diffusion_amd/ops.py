@@ -6,6 +6,7 @@ passed as ld, so column slices of wider buffers (fused QKV, concat buffers) are 
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -302,6 +303,22 @@ def groupnorm_bwd(X, dY, Radd, dX, gamma, beta, mean_rstd, dgamma, dbeta, coef, 
     _lib.call('da_groupnorm_bwd', x, ldx, dy, lddy, r, ldr, dx, lddx, _vec(gamma, C), _vec(beta, C),
               _f32buf(mean_rstd, B * G * 2), _vec(dgamma, C), _vec(dbeta, C), _f32buf(coef, B * G * 2),
               _f32buf(scratch, norm_scratch_floats(B, HW, C)), B, HW, C, G, int(silu), _stream())
+
+
+GN_PLAN_FIELDS = ('threads', 'nl', 'cw', 'parts', 'peers8', 'P', 'nchunks')
+
+
+def groupnorm_plan(B, HW, C, G, ld_min=None, ld_max=None, bwd=False) -> dict:
+    """the GroupNorm form da_groupnorm_fwd / _bwd runs for this call under the current options (da_groupnorm_plan_for):
+    {'form': 'resident' | 'multipass', 'threads', 'nl', 'cw', 'parts', 'peers8', 'P', 'nchunks'}; ld_min / ld_max are
+    the smallest / largest row stride of the call's tensors (default C)"""
+    out = (ctypes.c_int * 7)()
+    ld_min = C if ld_min is None else ld_min
+    ld_max = ld_min if ld_max is None else ld_max
+    form = _lib.load().da_groupnorm_plan_for(B, HW, C, G, ld_min, ld_max, int(bool(bwd)), out)
+    if form < 0:
+        raise ValueError(f'groupnorm_plan: arguments rejected ({B}, {HW}, {C}, {G}, {ld_min}, {ld_max})')
+    return dict(form='resident' if form == 1 else 'multipass', **dict(zip(GN_PLAN_FIELDS, out)))
 
 
 def layernorm_fwd(X, Y, gamma, beta, mean_rstd, eps=1e-5):

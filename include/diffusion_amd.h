@@ -148,6 +148,13 @@ int da_groupnorm_bwd(const void* X, long ldx, const void* dY, long lddy, const v
                      long lddx, const float* gamma, const float* beta, const float* mean_rstd, float* dgamma,
                      float* dbeta, float* coef, float* scratch, int B, int HW, int C, int G, int silu,
                      da_stream_t stream);
+/* which GroupNorm form da_groupnorm_fwd (bwd = 0) / da_groupnorm_bwd (bwd = 1) runs for (B, HW, C, G) under the current
+ * "gn_resident*" options, with ld_min / ld_max the smallest / largest row stride of its tensors (test / profiling label;
+ * changes nothing): 1 = single pass, 0 = multi-pass, -1 = arguments the entry points reject.  out[7] receives
+ * {threads, NL instantiation launched, CW, parts, peers8, P, nchunks}: the single-pass workgroup size, data vectors per
+ * thread, channels per workgroup, workgroups per image, 8-apart part placement and pixel lanes (nchunks 0), or for the
+ * multi-pass form {0, 0, C, 1, 0, 0, pixel chunks per image of the statistics pass}. */
+int da_groupnorm_plan_for(int B, int HW, int C, int G, long ld_min, long ld_max, int bwd, int* out);
 
 /* LayerNorm over rows of C.  Replaces torch.nn.LayerNorm / Composer LPLayerNorm (train.py:100-108) in
  * BasicTransformerBlock.  mean_rstd[M][2] saved for backward. */

@@ -127,6 +127,39 @@ def test_fastdiv_exact_at_the_admitted_bounds():
     assert any(fdiv(k * d - 1, d) != (k * d - 1) // d for k in range(1, 64))
 
 
+def test_groupnorm_plan_table_of_the_edge_tests():
+    """da_groupnorm_plan_for (host only) reports for every shape of tests/test_norm_edges_gpu.py's GN_CASES the instantiation
+    its table names, under every forced form; the table covers every forward NL, every backward (threads, NL) pair, peers8
+    on and off, one and several parts, line-aligned and unaligned slabs.  The query leaves the options as they were."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_norm_edges_gpu as E
+    from diffusion_amd import ops
+    fwd, bwd, peers8, parts, aligned = set(), set(), set(), set(), set()
+    for entry in E.GN_CASES:
+        for form in E.FORMS:
+            for b in (False, True):
+                p = E.gn_plan(ops, entry[0], form, b)
+                assert E.plan_label(p) == E.gn_target(entry, form, b), (entry[0], form, b, p)
+                if p['form'] == 'resident':
+                    (bwd if b else fwd).add((p['threads'], p['nl']))
+                    peers8.add(p['peers8'])
+                    parts.add(min(p['parts'], 2))
+                    aligned.add(p['cw'] * 2 % 128 == 0 and E.row_stride(entry[0][2], entry[0][4]) % 64 == 0)
+    assert fwd == {(1024, nl) for nl in (1, 2, 3, 4, 6, 8, 11, 16, 21)}
+    assert bwd == {(1024, nl) for nl in (1, 2, 3, 4, 6, 8, 11)} | {(768, 11), (768, 14)}
+    assert peers8 == {0, 1} and parts == {1, 2} and aligned == {False, True}
+    cpg = {C // G for (B, HW, C, G, *_), *_ in E.GN_CASES}
+    assert {1, 2, 3, 5, 8, 10, 15, 20, 30, 40, 60, 80} <= cpg
+    assert {HW for (B, HW, *_), *_ in E.GN_CASES} >= {1, 7, 16, 17, 1000}
+    # B = 1, HW = 1000 under the default options (restored by the forced forms): the multi-pass form with 62 chunks of
+    # 17 pixels, the last three empty
+    p = ops.groupnorm_plan(1, 1000, 320, 32, 336, 336)
+    assert p['form'] == 'multipass' and p['nchunks'] == 62 and 59 * -(-1000 // 62) >= 1000
+    with pytest.raises(ValueError):
+        ops.groupnorm_plan(1, 16, 320, 30)   # C % G != 0: rejected like the entry points
+
+
 def test_no_cpu_fallback():
     if torch.cuda.is_available():
         pytest.skip('GPU present')

@@ -748,6 +748,12 @@ def _gn_run(ops, dev, B, HW, C, silu, use_radd, pad):
     return x, gamma, beta, y, mr.clone(), dy, radd, dx, dg, db
 
 
+# (B, HW, C, bwd) of test_groupnorm_resident that no slab width fits (more than 21 / 14 vectors per thread): the forced
+# calls run the multi-pass kernels there, and the comparison with the multi-pass run is one of a form with itself
+_GN_NO_SLAB_FITS = {(8, 1024, 960, True), (1, 4096, 256, False), (1, 4096, 256, True), (2, 2304, 640, False),
+                    (2, 2304, 640, True)}
+
+
 @pytest.mark.parametrize('B,HW,C,silu,radd,pad', [
     (8, 1024, 320, 1, 1, 0), (8, 1024, 320, 0, 0, 16), (3, 1024, 640, 1, 1, 0), (8, 1024, 960, 1, 0, 0),
     (8, 256, 320, 1, 1, 0), (8, 256, 640, 1, 0, 64), (5, 256, 960, 0, 1, 0), (8, 256, 1280, 1, 1, 0), (8, 256, 1920, 1, 0, 0),
@@ -755,8 +761,10 @@ def _gn_run(ops, dev, B, HW, C, silu, use_radd, pad):
     (8, 16, 1280, 1, 1, 0), (16, 16, 2560, 1, 1, 0), (2, 100, 320, 1, 1, 16), (2, 1024, 512, 1, 0, 0), (1, 4096, 256, 1, 1, 0),
     (8, 256, 96, 1, 1, 0), (4, 49, 64, 0, 1, 16), (3, 1, 320, 1, 0, 0), (2, 2304, 640, 1, 1, 0)])
 def test_groupnorm_resident(ops, dev, B, HW, C, silu, radd, pad):
-    """The register-resident single-pass GroupNorm (forced: gn_resident=1) against torch fp32 and against the multi-pass
-    kernels on the same inputs, both thread forms of the backward; run to run bit-identical (fixed-order sums)."""
+    """The register-resident single-pass GroupNorm (forced: gn_resident=1, gn_resident_min_slab=0) against torch fp32 and
+    against the multi-pass kernels on the same inputs, both thread forms of the backward; run to run bit-identical
+    (fixed-order sums).  The plan query confirms that every forced call runs the resident kernels wherever a slab fits
+    (_GN_NO_SLAB_FITS lists where none does)."""
     G = 32
     try:
         ops.set_option('gn_resident', 0)
@@ -764,10 +772,17 @@ def test_groupnorm_resident(ops, dev, B, HW, C, silu, radd, pad):
         outs = []
         for form in (0, 2, 0):
             ops.set_option('gn_resident', 1)
+            ops.set_option('gn_resident_min_slab', 0)
             ops.set_option('gn_resident_form', form)
+            # x is a view of stride C + pad; y, dy, dx and Radd are dense
+            for bwd in (False, True):
+                plan = ops.groupnorm_plan(B, HW, C, G, C, C + pad, bwd=bwd)
+                want = 'multipass' if (B, HW, C, bwd) in _GN_NO_SLAB_FITS else 'resident'
+                assert plan['form'] == want, (form, 'bwd' if bwd else 'fwd', plan)
             outs.append(_gn_run(ops, dev, B, HW, C, silu, radd, pad))
     finally:
         ops.set_option('gn_resident', 192)
+        ops.set_option('gn_resident_min_slab', 64 * 1024)
         ops.set_option('gn_resident_form', 0)
     x, gamma, beta = base[0], base[1], base[2]
     xr = x.float().reshape(B, HW, C).permute(0, 2, 1).contiguous().requires_grad_(True)
