@@ -160,6 +160,99 @@ def test_groupnorm_plan_table_of_the_edge_tests():
         ops.groupnorm_plan(1, 16, 320, 30)   # C % G != 0: rejected like the entry points
 
 
+def test_gemm_edge_case_tables():
+    """tests/test_gemm_edges_gpu.py pins the kernel form of every case: da_gemm_nt_variant_for / da_gemm_tn_variant_for
+    (host only) must report the variant its table names under the case's options, so a dispatch change cannot move a
+    case unnoticed.  For the forms no query reports, each case meets the eligibility condition its table states.  The
+    queries leave the options as they were."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_gemm_edges_gpu as E
+    from diffusion_amd import _lib, ops
+    seen = set()
+    for case in E.NT_CASES:
+        cid, g, N, Cin, opts, want, epi, form = case
+        G = E.geom(ops, g)
+        M, K = G.B * G.Hout * G.Wout, G.ksize * G.ksize * Cin
+        if want is not None:
+            assert E.nt_variant(ops, case) == want, (cid, E.nt_variant(ops, case))
+            seen.add(want)
+        if form == 'pconv':   # launch_v2: 3x3 mode 0, N % 320 == 0, tiles > 256 - reserve_cus, a ragged last row tile
+            tiles = -(-M // 256) * (N // 320)
+            assert G.ksize == 3 and G.mode == 0 and N % 320 == 0 and tiles > 256 - opts.get('reserve_cus', 0), cid
+            assert M % 256 != 0, cid
+        if form.endswith('-early'):   # the 16-wave forms take ksize 1 through the early-issue persistent walk
+            assert G.ksize == 1 and opts['gemm_nt_variant'] in (12, 14, 15, 18), cid
+        if form == 'ws':   # da_gemm_nt_ws_try: K 320 (BN 320, N <= 1280) / 640 (BN 128), whole 32-row tiles, enough tiles
+            bn = 320 if K == 320 else 128
+            assert K in (320, 640) and M % 32 == 0 and N % bn == 0 and N // bn <= 8, cid
+            assert (M // 32) * (N // bn) >= 8 * (256 - opts['reserve_cus']) and not {'rb', 'a', 'f32'} & set(epi.split('+'))
+        if form == 'stream':   # da_gemm_nt_v3_try: K % 64 == 0, K >= 320, bf16 out, alpha 1, no row bias
+            assert K % 64 == 0 and K >= 320 and not {'rb', 'a', 'f32'} & set(epi.split('+')), cid
+    assert seen == {1, 4, 5, 10, 11, 12, 14, 15, 16, 18}
+    forms = {c[7] for c in E.NT_CASES}
+    assert {'pconv', 'splitk', 'ws', 'stream', 'v12-early', 'v14-early', 'v15-early', 'v18-early'} <= forms
+    assert {0, 1, 3} <= {c[4].get('gemm_nt_de', 1) for c in E.NT_CASES}
+    assert {0, 1} <= {c[4].get('gemm_nt_korder', 1) for c in E.NT_CASES if c[3] in (320, 1280) and c[1][0] == 'conv'}
+    modes = {E.geom(ops, c[1]).mode for c in E.NT_CASES}
+    assert modes == {0, 1, 2, 3, 4}
+    tn_seen = set()
+    for case in E.TN_CASES:
+        cid, g, N, Cin, opts, want, use_ws, use_db, form = case
+        assert E.tn_variant(ops, case) == want, (cid, E.tn_variant(ops, case))
+        tn_seen.add(form)
+        G = E.geom(ops, g)
+        M = G.B * G.Hout * G.Wout
+        if form == 'v1':
+            assert M <= 256, cid      # one pixel split
+        if form in ('v1slab', 'v1atomic'):
+            assert M > 256 and use_ws == (form == 'v1slab'), cid
+        if form in ('v2slab', 'v2atomic'):
+            assert M >= 1024 and use_ws == (form == 'v2slab'), cid
+        if form.startswith('ring'):
+            assert G.ksize == 1 and G.mode == 0 and want == 3, cid
+    assert tn_seen == {'v1', 'v1slab', 'v1atomic', 'v2', 'fast', 'v2slab', 'v2atomic', 'ring4', 'ring5'}
+    assert _lib.load().da_gemm_nt_variant_for(4096, 1280, 2880, 320, 0) == ops._lib.load().da_gemm_nt_variant_for(
+        4096, 1280, 2880, 320, 0)   # defaults restored
+
+
+def test_gemm_edge_gather_matches_conv2d():
+    """the explicit gather of tests/test_gemm_edges_gpu.py, times the weights, equals the float64 convolution it stands
+    for in every mode: 0 (pad 1, and 1x1), 1 (stride 2, pad 1, odd sizes too), 2 (dgrad of stride 2), 3 (nearest-2x
+    upsample), 4 (stride 2, bottom / right pad)"""
+    import sys
+    import torch.nn.functional as F
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_gemm_edges_gpu as E
+    from diffusion_amd import ops
+    g = torch.Generator().manual_seed(3)
+    Cin, Co = 8, 16
+    for kind, B, H, W in (('conv', 2, 1, 1), ('conv', 2, 3, 5), ('c1', 2, 3, 5), ('down', 2, 4, 6), ('down', 2, 3, 5),
+                          ('down', 1, 1, 1), ('dgrad', 2, 4, 6), ('dgrad', 1, 2, 2), ('up', 2, 1, 1), ('up', 2, 3, 5),
+                          ('vae', 2, 4, 6), ('vae', 1, 2, 2)):
+        G = E.geom(ops, (kind, B, H, W))
+        k = G.ksize
+        x = torch.randn(B, Cin, G.Hin, G.Win, generator=g, dtype=torch.float64)
+        w = torch.randn(Co, Cin, k, k, generator=g, dtype=torch.float64)
+        if kind in ('conv', 'c1'):
+            ref = F.conv2d(x, w, padding=k // 2)
+        elif kind == 'down':
+            ref = F.conv2d(x, w, stride=2, padding=1)
+        elif kind == 'up':
+            ref = F.conv2d(F.interpolate(x, scale_factor=2, mode='nearest'), w, padding=1)
+        elif kind == 'vae':
+            ref = F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2)
+        else:   # dgrad: the gradient of a stride-2 conv (weights w2 [Cin, Co]) wrt its input, weights flipped + transposed
+            w2 = torch.randn(Cin, Co, 3, 3, generator=g, dtype=torch.float64)
+            ref = F.conv_transpose2d(x, w2, stride=2, padding=1, output_padding=1)
+            w = w2.flip(2, 3).transpose(0, 1)    # [Co, Cin, 3, 3]: Wt[co][r][s][ci] = w2[ci][co][2-r][2-s]
+        assert tuple(ref.shape[2:]) == (G.Hout, G.Wout), (kind, ref.shape, G.Hout, G.Wout)
+        X = x.permute(0, 2, 3, 1).reshape(-1, Cin)
+        Wm = w.permute(0, 2, 3, 1).reshape(Co, -1)
+        got = (E.gather(X, G) @ Wm.t()).view(B, G.Hout, G.Wout, Co).permute(0, 3, 1, 2)
+        assert torch.allclose(got, ref, rtol=0, atol=1e-12), kind
+
+
 def test_no_cpu_fallback():
     if torch.cuda.is_available():
         pytest.skip('GPU present')

@@ -211,8 +211,10 @@ def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant, de):
     """The direct epilogue (accumulators -> bf16 -> v_permlane16_swap -> 16-byte stores, residual fetched in the same lane
     layout; da_set_option('gemm_nt_de', 1), the default) against the LDS strip epilogue it replaces (0): same sums, same
     roundings, so every form must agree BIT FOR BIT - linears (persistent walk), 3x3 convolutions with the per-image row
-    bias and a residual (one tile per workgroup, and the persistent convolution walk at a forced grid), stride 2, its
-    dgrad, the fused upsample, ragged row / column tails, strided views, an in-place residual.  de = 2 / 3 (opt-in) also
+    bias and a residual (one tile per workgroup; for variant 12 also the persistent convolution walk, which takes a
+    3x3 conv with N % 320 == 0 and more tiles than usable CUs: 136 tiles against the 128 CUs left by reserve_cus 128,
+    the last row tile ragged, at the default and at a forced grid), stride 2, its dgrad, the fused upsample, ragged row /
+    column tails, strided views, an in-place residual.  de = 2 / 3 (opt-in) also
     send the linears without / with a residual through the direct epilogue: 1 leaves them on the strip epilogue on both
     sides of the comparison."""
     ops.set_option('gemm_nt_variant', variant)
@@ -244,6 +246,21 @@ def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant, de):
         ops.set_option('gemm_nt_persist', -1)
         ref = F.conv2d(x.float(), w.float(), cb, padding=1) + rb.float()[:, :, None, None]
         check(from_nhwc(outs[5], B, H, Wd), ref + from_nhwc(Rc.float(), B, H, Wd), what='conv3x3 rowbias+res')
+        Bp, Cop = 133, 1280     # M = 8512 = 33 x 256 + 64: 34 x 4 tiles of 256 x 320
+        xp = rnd(Bp, C, 8, 8, dev=dev, seed=11).to(BF)
+        wp = rnd(Cop, C, 3, 3, dev=dev, seed=12, scale=(9 * C)**-0.5).to(BF)
+        rbp = rnd(Bp, Cop, dev=dev, seed=13).to(BF); Rp = rnd(Bp * 64, Cop, dev=dev, seed=14).to(BF)
+        cbp = rnd(Cop, dev=dev, seed=15)
+        ops.set_option('reserve_cus', 128)
+        for grid in (-1, 3):
+            ops.set_option('gemm_nt_persist', grid)
+            o = torch.empty(Bp * 64, Cop, device=dev, dtype=BF)
+            ops.gemm_nt(nhwc(xp), w_ohwi(wp), o, ops.Geom.conv(Bp, 8, 8), bias=cbp, rowbias=rbp, residual=Rp)
+            outs.append(o)
+        ops.set_option('reserve_cus', 0)
+        ops.set_option('gemm_nt_persist', -1)
+        refp = F.conv2d(xp.float(), wp.float(), cbp, padding=1) + rbp.float()[:, :, None, None]
+        check(from_nhwc(outs[-1], Bp, 8, 8), refp + from_nhwc(Rp.float(), Bp, 8, 8), what='persistent conv3x3, ragged tail')
         o2 = torch.empty(B * (H // 2) * (Wd // 2), Co, device=dev, dtype=BF)
         ops.gemm_nt(nhwc(x), w_ohwi(w), o2, ops.Geom.down(B, H, Wd), bias=cb)
         outs.append(o2)
@@ -274,6 +291,7 @@ def test_gemm_nt_direct_epilogue_equals_strip_epilogue(ops, dev, variant, de):
     finally:
         ops.set_option('gemm_nt_de', 1)
         ops.set_option('gemm_nt_persist', -1)
+        ops.set_option('reserve_cus', 0)
         ops.set_option('gemm_nt_variant', 0)
     for i, (r, g_) in enumerate(zip(ref, got)):
         assert torch.equal(r, g_), f'form {i}: {(r.float() - g_.float()).abs().max().item()}'
