@@ -13,6 +13,14 @@ LIB_PATH = os.path.join(_HERE, os.environ.get('DA_LIB_ALT') or 'libdiffusion_amd
 
 _vp, _l, _i, _f, _fp, _ll = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_void_p, C.c_void_p
 
+
+
+class DaWgradItem(C.Structure):
+    """one linear layer of da_gemm_tn_wgrad_group (struct DaWgradItem of include/diffusion_amd.h)"""
+    _fields_ = [('dY', C.c_void_p), ('lddy', C.c_long), ('X', C.c_void_p), ('ldx', C.c_long), ('dW', C.c_void_p),
+                ('dbias', C.c_void_p), ('N', C.c_int), ('Cin', C.c_int)]
+
+
 # name -> argtypes (must mirror include/diffusion_amd.h exactly)
 SIGNATURES = {
     'da_gemm_nt': [_vp, _l, _vp, _vp, _l, _fp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _fp, _l,
@@ -23,6 +31,8 @@ SIGNATURES = {
     'da_gemm_nt_geglu_bwd': [_vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _i, _vp],
     'da_gemm_tn_wgrad': [_vp, _l, _vp, _l, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _l, _vp],
     'da_gemm_tn_variant_for': [_i, _i, _i, _i, _i, _i, _i, _i, _i],
+    'da_gemm_tn_wgrad_group': [C.POINTER(DaWgradItem), _i, _i, _fp, _l, _vp],
+    'da_gemm_tn_group_plan': [C.POINTER(DaWgradItem), _i, _i, _l, C.POINTER(_i), _i, C.POINTER(_i)],
     'da_attn_fwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _i, _i, _i, _i, _f, _vp],
     'da_attn_fwd_causal': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _i, _i, _i, _f, _vp],
     'da_attn_bwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _fp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i,

@@ -213,7 +213,7 @@ int g_tn_variant = 0;  // 0 auto, 1 force v1 (128x128x32), 2 force v2 (320x192x6
 // zero fill of the flat gradient nor the read half of 866 M read-add-writes.  0 (default) = accumulate, as the header says.
 int g_grad_overwrite = 0;
 
-static bool tn_takes_v2(int M, int N, int Kt) {
+bool da_tn_takes_v2(int M, int N, int Kt) {  // also the eligibility test of the grouped form (gemm_tn_v2.hip)
   // measured (tools/tn_ab.py, microbatch 16 / 64): the 320x192x64 kernel wins from 1,024 pixels up (1.1-2.3x), and at 256
   // pixels once the gradient itself is large (N * K' >= 8 M elements: 1.2-1.5x; below that the 128x128x32 kernel is 1.4x
   // faster)
@@ -222,7 +222,7 @@ static bool tn_takes_v2(int M, int N, int Kt) {
 }
 
 extern "C" int da_gemm_tn_variant_for(int M, int N, int Cin, int Hin, int Win, int Hout, int Wout, int ksize, int mode) {
-  if (!tn_takes_v2(M, N, ksize * ksize * Cin)) return 1;
+  if (!da_tn_takes_v2(M, N, ksize * ksize * Cin)) return 1;
   return da_gemm_tn_v2_fast_period(M, N, Hin, Win, Hout, Wout, mode) ? 3 : 2;
 }
 
@@ -240,7 +240,7 @@ extern "C" int da_gemm_tn_wgrad(const void* dY, long lddy, const void* X, long l
   if (ksize == 3 && ((long)M * Hout * Wout >= (1L << 40) || 9L * Cin * Cin >= (1L << 40))) return DA_ERR_SHAPE;
   {
     const int Kt = ksize * ksize * Cin;
-    if (tn_takes_v2(M, N, Kt))
+    if (da_tn_takes_v2(M, N, Kt))
       return da_gemm_tn_v2_dispatch(g_tn_variant == 2 ? 2 : 3, dY, lddy, X, ldx, dW, dbias, M, N, Cin, Hin, Win, Hout, Wout, ksize, mode,
                                     split_ws, split_ws ? split_ws_floats : 0, stream);
   }

@@ -64,6 +64,80 @@ DEVINL void glds16_tn(const void* gsrc, char* lds_dst) {
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
+// gemm_tn2_group_kernel's half-step (32 pixels = one MFMA K-step of a wave's 80 x 96 block): gemm_tn2_kernel's compute_half_at,
+// instruction for instruction, as a function (that kernel keeps its lambda: moving it changed its register allocation).
+// Ab / Bb: LDS byte offsets of the dY / X images.
+template <int T2_BK, bool FAST, bool CT>
+DEVINL void tn2_compute_half(const unsigned Ab, const unsigned Bb, int ms, int wa, int wb, int lane, bool do_bias,
+                             f32x4 (&acc)[5][T2_BK / 32], f32x4 (&accb)[5]) {
+  constexpr int T2_SB = T2_BK * 2;
+  constexpr int JT = T2_BK / 32;
+  typedef __attribute__((ext_vector_type(8))) short short8v;
+  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+  bf16x8 ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = (bf16)1.0f;
+  const int r0 = ms * 32 + 4 * g + q, r1 = r0 + 16;
+  short4v ta0[5], ta1[5], tb0[JT], tb1[JT];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const int ch = wa * 10 + i * 2 + (pp >> 1);
+    ta0[i] = lds_tr16_b64_asm(Ab + r0 * T2_SA + ((ch ^ swA(r0)) << 4) + 8 * (pp & 1));
+    ta1[i] = lds_tr16_b64_asm(Ab + r1 * T2_SA + ((ch ^ swA(r1)) << 4) + 8 * (pp & 1));
+  }
+  auto read_b = [&](int jj) {
+    const int ch = wb * (JT * 2) + jj * 2 + (pp >> 1);
+    tb0[jj] = lds_tr16_b64_asm(Bb + r0 * T2_SB + ((ch ^ swB<T2_BK>(r0)) << 4) + 8 * (pp & 1));
+    tb1[jj] = lds_tr16_b64_asm(Bb + r1 * T2_SB + ((ch ^ swB<T2_BK>(r1)) << 4) + 8 * (pp & 1));
+  };
+  static_assert(JT == 6, "counted waits below assume 6 X fragments per wave");
+  // FAST has the registers to request all six X fragments at once; the generic path (more live gather state)
+  // requests the second three only after the first MFMA block, which keeps it free of spills
+#pragma unroll
+  for (int jj = 0; jj < (FAST ? JT : JT / 2); ++jj) read_b(jj);
+  if constexpr (FAST)
+    lds_wait_for<6>(ta0[0], ta1[0], ta0[1], ta1[1], ta0[2], ta1[2], ta0[3], ta1[3], ta0[4], ta1[4], tb0[0], tb1[0],
+                    tb0[1], tb1[1], tb0[2], tb1[2]);
+  else
+    lds_wait_for<0>(ta0[0], ta1[0], ta0[1], ta1[1], ta0[2], ta1[2], ta0[3], ta1[3], ta0[4], ta1[4], tb0[0], tb1[0],
+                    tb0[1], tb1[1], tb0[2], tb1[2]);
+  bf16x8 a[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    short8v v = __builtin_shufflevector(ta0[i], ta1[i], 0, 1, 2, 3, 4, 5, 6, 7);
+    a[i] = __builtin_bit_cast(bf16x8, v);
+  }
+  if (do_bias) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      accb[i] = CT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, a[i], accb[i], 0, 0, 0)
+                   : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], ones, accb[i], 0, 0, 0);
+  }
+#pragma unroll
+  for (int jh = 0; jh < 2; ++jh) {
+    if (jh == 1) {
+      if constexpr (!FAST) {
+#pragma unroll
+        for (int jj = JT / 2; jj < JT; ++jj) read_b(jj);
+      }
+      lds_wait_for<0>(tb0[3], tb1[3], tb0[4], tb1[4], tb0[5], tb1[5]);
+    }
+    bf16x8 bfr[JT / 2];
+#pragma unroll
+    for (int jj = 0; jj < JT / 2; ++jj) {
+      short8v v = __builtin_shufflevector(tb0[jh * (JT / 2) + jj], tb1[jh * (JT / 2) + jj], 0, 1, 2, 3, 4, 5, 6, 7);
+      bfr[jj] = __builtin_bit_cast(bf16x8, v);
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+      for (int jj = 0; jj < JT / 2; ++jj)
+        acc[i][jh * (JT / 2) + jj] =
+            CT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[jj], a[i], acc[i][jh * (JT / 2) + jj], 0, 0, 0)
+               : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], bfr[jj], acc[i][jh * (JT / 2) + jj], 0, 0, 0);
+  }
+}
+
 // T2_BK: output tile columns (k'): 192 (256 also fits the swizzle scheme but spills registers).
 // FAST: stride-1 gather (mode 0) with M % 64 == 0 and a border pattern that repeats every p.period <= 64 steps
 // (HW % 64 == 0, or 64 % HW == 0 with period 1) - every stride-1 3x3 conv and every linear layer of the U-Net.  There the
@@ -565,25 +639,241 @@ __global__ __launch_bounds__(256) void tn_slab_reduce_kernel(GemmTN2Params p, in
   }
 }
 
-template <int BK, bool FAST>
-int launch_tn2(GemmTN2Params p, float* ws, long ws_floats, hipStream_t stream) {
-  constexpr int SMEM = 2 * (T2_A_BYTES + T2_MS * BK * 2);
-  p.tiles_n = (p.N + T2_BN - 1) / T2_BN;
-  p.tiles_k = (p.Kt + BK - 1) / BK;
-  const int tiles = p.tiles_n * p.tiles_k;
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Grouped form (da_gemm_tn_wgrad_group): the linear-layer weight gradients of one transformer block in ONE launch.  A linear
+// layer has 2-28 tiles of 320 x 192, so alone it needs 9-125 pixel splits to fill the chip, each storing a whole fp32 tile
+// as a slab; the 39-556 tiles of a block's eight layers together fill it with 1-13 splits.  The K loop is gemm_tn2_kernel's
+// FAST ksize-1 loop (same tile, LDS images, swizzles, tn2_compute_half); only the block decode differs: the id maps to
+// (item, split, tn, tk) through the item table in the kernel argument - everything taken from the item is wave-uniform.
+constexpr int TN_GROUP_MAX = 16;  // items per launch (the table travels by value: 16 x 88 B)
+
+struct TnGroupItem {
+  const bf16* dY;
+  const bf16* X;
+  float* dW;
+  float* dbias;
+  long slab_off, bslab_off;  // floats from TnGroupParams::slab: tile partials [tn][split][320][Kt], bias partials [tn][split][320]
+  int lddy, ldx, N, Kt, tiles_n, tiles_k;
+  int first;            // first logical workgroup id of the item
+  int rfirst, rblocks;  // reduce launch: first block and block count of the item's dW
+  int bfirst;           // reduce launch: first bias block (behind all dW blocks; 16 bias elements per block)
+};
+
+struct TnGroupParams {
+  TnGroupItem it[TN_GROUP_MAX];
+  float* slab;
+  int n_items, splits, m_per_split, M, nblk, overwrite;
+};
+
+// CT = true: splits == 1, the workgroup owns its tile (transposed products, 16-byte read-add-write of dW);
+// CT = false: splits > 1, partial tiles and bias partials are stored as slabs (columns < Kt and rows < N only).
+template <bool CT>
+__global__ __launch_bounds__(512, 2) void gemm_tn2_group_kernel(TnGroupParams p) {
+  constexpr int BK = 192, SB = BK * 2, B_BYTES = T2_MS * SB, STAGE = T2_A_BYTES + B_BYTES;
+  constexpr int BJ = B_BYTES / 1024 / 8, C16B = SB / 16, JT = BK / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wa = wave >> 1, wb = wave & 1;
+
+  // XCD-aware order as in gemm_tn2_kernel: each XCD gets a contiguous run of logical ids, and the ids of one (item, split)
+  // are adjacent, k'-tile fastest, then n-tile - the workgroups running together on an XCD stream the same dY / X rows
+  int bid = blockIdx.x;
+  {
+    const int q = p.nblk >> 3, r = p.nblk & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  int item = 0;
+  for (int i = 1; i < p.n_items; ++i)
+    if (bid >= p.it[i].first) item = i;
+  const TnGroupItem& I = p.it[item];
+  const int N = I.N, Kt = I.Kt, lddy = I.lddy, ldx = I.ldx;
+  int local = bid - I.first;
+  const int tk = local % I.tiles_k;
+  local /= I.tiles_k;
+  const int tn = local % I.tiles_n;
+  const int split = local / I.tiles_n;
+  const int n0 = tn * T2_BN, k0 = tk * BK;
+  const int m_begin = split * p.m_per_split;
+  const int m_end = min(p.M, m_begin + p.m_per_split);
+  const int nsteps = (m_end - m_begin) / T2_MS;  // M and m_per_split are multiples of 64; the host leaves no split empty
+
+  // DMA source offsets of a lane's pieces relative to the step's first row (fixed for the whole kernel); columns past
+  // N / Kt are clamped: their products are never stored
+  unsigned fa_off[T2_AJ], fx_off[BJ];
+#pragma unroll
+  for (int j = 0; j < T2_AJ; ++j) {
+    const int ci = (wave * T2_AJ + j) * 64 + lane;
+    const int row = ci / 40, pc = ci - row * 40;
+    const int n = min(n0 + (pc ^ swA(row)) * 8, N - 8);
+    fa_off[j] = (unsigned)(row * lddy + n);
+  }
+#pragma unroll
+  for (int j = 0; j < BJ; ++j) {
+    const int ci = (wave * BJ + j) * 64 + lane;
+    const int row = ci / C16B, pc = ci - row * C16B;
+    const int kk = min(k0 + (pc ^ swB<BK>(row)) * 8, Kt - 8);
+    fx_off[j] = (unsigned)(row * ldx + kk);
+  }
+  const bf16* dY = I.dY;
+  const bf16* X = I.X;
+  int mcur = m_begin;
+  auto issue = [&](int stage, bool live) {
+    char* Ab = smem + stage * STAGE;
+    char* Bb = Ab + T2_A_BYTES;
+    const int mc = live ? mcur : m_begin;  // the step after the last re-reads step 0 into the free stage
+    const bf16* ab = dY + (long)mc * lddy;
+    const bf16* xb = X + (long)mc * ldx;
+#pragma unroll
+    for (int j = 0; j < T2_AJ; ++j) glds16_tn(ab + fa_off[j], Ab + (wave * T2_AJ + j) * 1024);
+#pragma unroll
+    for (int j = 0; j < BJ; ++j) glds16_tn(xb + fx_off[j], Bb + (wave * BJ + j) * 1024);
+    mcur += T2_MS;
+  };
+
+  f32x4 acc[5][JT];
+#pragma unroll
+  for (int i = 0; i < 5; ++i)
+#pragma unroll
+    for (int j = 0; j < JT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_bias = (I.dbias != nullptr) && (tk == 0) && (wb == 0);
+  f32x4 accb[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const unsigned smem_off = lds_offset(smem);
+  issue(0, true);
+  __syncthreads();
+  for (int t = 0; t < nsteps; ++t) {  // one basic block, the request first: as gemm_tn2_kernel's FAST loop
+    issue((t + 1) & 1, t + 1 < nsteps);
+    const unsigned Ab = smem_off + (t & 1) * STAGE;
+    tn2_compute_half<BK, true, CT>(Ab, Ab + T2_A_BYTES, 0, wa, wb, lane, do_bias, acc, accb);
+    tn2_compute_half<BK, true, CT>(Ab, Ab + T2_A_BYTES, 1, wa, wb, lane, do_bias, acc, accb);
+    __syncthreads();
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail request writes LDS: not past the end of the workgroup
+
+  if constexpr (CT) {
+    // accumulator register e of tile (i, j): n = wa*80 + i*16 + (lane & 15), k' = wb*96 + j*16 + 4*(lane >> 4) + e
+    float* dW = I.dW;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+      for (int j = 0; j < JT; ++j) {
+        const int n = n0 + wa * 80 + i * 16 + (lane & 15), kc = k0 + wb * (16 * JT) + j * 16 + (lane >> 4) * 4;
+        if (n < N && kc < Kt) {  // Kt % 8 == 0 and kc % 4 == 0: the four k' are inside together
+          f32x4* dst = reinterpret_cast<f32x4*>(dW + (long)n * Kt + kc);
+          if (p.overwrite) *dst = acc[i][j];
+          else *dst += acc[i][j];
+        }
+      }
+    if (do_bias && lane < 16) {  // every register of accb[i] holds the column sum of n = wa*80 + i*16 + lane
+      float* db = I.dbias;
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        const int n = n0 + wa * 80 + i * 16 + lane;
+        if (n < N) db[n] = p.overwrite ? accb[i][0] : db[n] + accb[i][0];
+      }
+    }
+  } else {
+    float* slab = p.slab + I.slab_off + ((long)(tn * p.splits + split) * T2_BN) * Kt;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+      for (int j = 0; j < JT; ++j) {
+        const int kc = k0 + wb * (16 * JT) + j * 16 + (lane & 15);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int nl = wa * 80 + i * 16 + (lane >> 4) * 4 + e;
+          if (n0 + nl < N && kc < Kt) slab[(long)nl * Kt + kc] = acc[i][j][e];
+        }
+      }
+    if (do_bias && (lane & 15) == 0) {
+      float* bslab = p.slab + I.bslab_off + (long)(tn * p.splits + split) * T2_BN;
+#pragma unroll
+      for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int nl = wa * 80 + i * 16 + (lane >> 4) * 4 + e;
+          if (n0 + nl < N) bslab[nl] = accb[i][e];
+        }
+    }
+  }
+}
+
+// The reduce of a grouped launch, all items in one grid: the additions of tn_slab_reduce_kernel (eight chains over the splits,
+// fixed order; bias: 16 lanes per element on two chains, then a fixed butterfly) over the compact slabs above.
+__global__ __launch_bounds__(256) void tn_group_reduce_kernel(TnGroupParams p, int main_blocks) {
+  int b = blockIdx.x;
+  if (b >= main_blocks) {
+    b -= main_blocks;
+    int item = 0;
+    for (int i = 1; i < p.n_items; ++i)
+      if (b >= p.it[i].bfirst) item = i;
+    const TnGroupItem& I = p.it[item];
+    const int grp = threadIdx.x >> 4, l = threadIdx.x & 15;
+    const int n = (b - I.bfirst) * 16 + grp;
+    if (n < I.N) {
+      const int tn = n / T2_BN;
+      const float* src = p.slab + I.bslab_off + ((long)tn * p.splits) * T2_BN + (n - tn * T2_BN);
+      float a0 = 0.f, a1 = 0.f;
+      int sp = l;
+      for (; sp + 16 < p.splits; sp += 32) {
+        a0 += src[(long)sp * T2_BN];
+        a1 += src[(long)(sp + 16) * T2_BN];
+      }
+      if (sp < p.splits) a0 += src[(long)sp * T2_BN];
+      float a = a0 + a1;
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o, 16);
+      if (l == 0) I.dbias[n] = p.overwrite ? a : I.dbias[n] + a;
+    }
+    return;
+  }
+  int item = 0;
+  for (int i = 1; i < p.n_items; ++i)
+    if (b >= p.it[i].rfirst) item = i;
+  const TnGroupItem& I = p.it[item];
+  const int Kt = I.Kt, kq = Kt >> 2;
+  const long total = (long)I.N * kq;
+  const long sstride = (long)T2_BN * Kt;  // floats between two splits of a tile row
+  for (long i = (long)(b - I.rfirst) * 256 + threadIdx.x; i < total; i += (long)I.rblocks * 256) {
+    const int n = (int)(i / kq);
+    const int kc = (int)(i - (long)n * kq) * 4;
+    const int tn = n / T2_BN;
+    const float* src = p.slab + I.slab_off + ((long)(tn * p.splits) * T2_BN + (n - tn * T2_BN)) * Kt + kc;
+    f32x4 acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int sp = 0;
+    for (; sp + 7 < p.splits; sp += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc[u] += *reinterpret_cast<const f32x4*>(src + (long)(sp + u) * sstride);
+    }
+    for (int u = 0; sp < p.splits; ++sp, ++u) acc[u & 7] += *reinterpret_cast<const f32x4*>(src + (long)sp * sstride);
+    f32x4* dst = reinterpret_cast<f32x4*>(I.dW + (long)n * Kt + kc);
+    const f32x4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    *dst = p.overwrite ? sum : *dst + sum;
+  }
+}
+
+// split count of a per-layer launch (launch_tn2) for `tiles` output tiles over M pixels on ncu CUs
+static int tn2_pick_splits(int tiles, int M, int ncu) {
   // One 512-thread workgroup per CU; the pixel range is split into k parts so that tiles*k fills the CUs (256, less the
   // ones da_set_option("reserve_cus") leaves to an overlapping collective).
   //  * tiles >= 90 % of the CUs: k = 1 - the workgroup owns its tile, plain read-add-write, no slabs;
   //  * otherwise the smallest k whose grid is (nearly) a whole number of rounds (last round >= 90 % full),
   //    capped so that the k extra fp32 tile writes stay below ~20 % of the GEMM time
   //    (k <= M/6000) but never below one full round; fallback: the fullest grid within the cap.
-  const int ncu = da_usable_cus(256);
   int best = 1;
   if (tiles < (ncu * 29) / 32) {
-    int kcap = p.M / 6000;
+    int kcap = M / 6000;
     const int one_round = (ncu + tiles - 1) / tiles;
     if (kcap < one_round) kcap = one_round;
-    const int max_splits = p.M / 512 > 0 ? p.M / 512 : 1;
+    const int max_splits = M / 512 > 0 ? M / 512 : 1;
     if (kcap > max_splits) kcap = max_splits;
     double best_eff = -1.0;
     bool found = false;
@@ -602,6 +892,16 @@ int launch_tn2(GemmTN2Params p, float* ws, long ws_floats, hipStream_t stream) {
     }
     (void)found;
   }
+  return best;
+}
+
+template <int BK, bool FAST>
+int launch_tn2(GemmTN2Params p, float* ws, long ws_floats, hipStream_t stream) {
+  constexpr int SMEM = 2 * (T2_A_BYTES + T2_MS * BK * 2);
+  p.tiles_n = (p.N + T2_BN - 1) / T2_BN;
+  p.tiles_k = (p.Kt + BK - 1) / BK;
+  const int tiles = p.tiles_n * p.tiles_k;
+  const int best = tn2_pick_splits(tiles, p.M, da_usable_cus(256));
   int mps = (p.M + best - 1) / best;
   mps = ((mps + T2_MS - 1) / T2_MS) * T2_MS;
   p.splits = (p.M + mps - 1) / mps;
@@ -696,4 +996,270 @@ int da_gemm_tn_v2_dispatch(int variant, const void* dY, long lddy, const void* X
   p.period = da_gemm_tn_v2_fast_period(M, N, Hin, Win, Hout, Wout, mode);
   p.ups64 = (p.period && mode == 3 && Wout == T2_MS) ? 1 : 0;
   return p.period ? launch_tn2<192, true>(p, ws, ws_floats, stream) : launch_tn2<192, false>(p, ws, ws_floats, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Grouped weight gradients: the plan (pure function of the shapes and options) and the launch.
+int g_tn_ungroup = 0;        // da_set_option("gemm_tn_ungroup", 1): da_gemm_tn_wgrad_group runs its items one by one
+bool da_tn_takes_v2(int M, int N, int Kt);  // gemm_tn.hip
+
+namespace {
+
+// Cost of a launch of `tiles` 320 x 192 tiles over M pixels in s pixel splits, in microseconds:
+//     rounds(tiles * s / CUs) x (64-pixel steps per workgroup x STEP + FIXED)  [+ REDUCE + 2 x slab bytes / SLAB_BW  when s > 1]
+// Constants from the per-shape times of the batch-256 step (profiles/r04_per_shape_in_situ.txt; one workgroup per CU):
+//   STEP   1.8 us: 262144 x 2560 x 320 (16 tiles x 16 splits, 256 steps) takes 505 us, 31 us of them slab traffic -> 1.85 us;
+//                  the 3x3 convolutions' 1.1-1.29 PFLOP/s are 1.55-1.8 us; the HBM-bound 320 x 320 linears alone 2.3 us
+//   FIXED  10 us:  launch + prologue + the tile store of a workgroup (16384 x 1280 x 1280: 78.6 us - 29 steps - 31 us of slabs)
+//   SLAB_BW 4 TB/s for a slab byte written and read again (61 MB slabs: ~31 us of the K' <= 1280 linears), REDUCE 6 us per launch
+// Checked on a block's eight linears at batch 256 (tools/tn_group_ab.py, profiles/wgrad_group_per_level.txt): the model gives
+// 1227 / 1214 us for the plans of the 320 / 1280-channel levels, measured 1217 / 1100 us (per-layer: 1379 / 1239 us).
+constexpr double TNG_STEP_US = 1.8, TNG_FIXED_US = 10.0, TNG_REDUCE_US = 6.0, TNG_SLAB_BYTES_PER_US = 4.0e6;
+
+struct TnGroupShape {
+  int N, Kt, bias;
+};
+
+inline int tng_tiles(const TnGroupShape& it) { return ((it.N + T2_BN - 1) / T2_BN) * ((it.Kt + 191) / 192); }
+
+// effective split count and pixels per split for a requested split count
+inline int tng_splits(int M, int s, int* mps_out) {
+  int mps = (M + s - 1) / s;
+  mps = ((mps + T2_MS - 1) / T2_MS) * T2_MS;
+  if (mps_out) *mps_out = mps;
+  return (M + mps - 1) / mps;
+}
+
+// workspace floats of a grouped launch with s > 1 splits (compact slabs: live columns only)
+inline long tng_slab_floats(const TnGroupShape* its, int n, int s) {
+  long f = 0;
+  for (int i = 0; i < n; ++i) {
+    const long tn = (its[i].N + T2_BN - 1) / T2_BN;
+    f += tn * s * T2_BN * its[i].Kt + (its[i].bias ? tn * s * T2_BN : 0);
+  }
+  return f;
+}
+
+inline double tng_cost(long tiles, int M, int s, int mps, long slab_floats, int ncu) {
+  const long rounds = (tiles * s + ncu - 1) / ncu;
+  double t = (double)rounds * ((mps / T2_MS) * TNG_STEP_US + TNG_FIXED_US);
+  if (s > 1) t += TNG_REDUCE_US + 2.0 * 4.0 * (double)slab_floats / TNG_SLAB_BYTES_PER_US;
+  return t;
+}
+
+// per-layer cost of one item: launch_tn2's split policy (whole 320 x 192 tile slabs) under the same cost function
+double tng_layer_cost(const TnGroupShape& it, int M, int ncu) {
+  const int t = tng_tiles(it);
+  int mps;
+  const int s = tng_splits(M, tn2_pick_splits(t, M, ncu), &mps);
+  const long tn = (it.N + T2_BN - 1) / T2_BN;
+  return tng_cost(t, M, s, mps, s > 1 ? (long)t * s * T2_BN * 192 + (it.bias ? tn * s * T2_BN : 0) : 0, ncu);
+}
+
+// ONE grouped launch over its[0..n): the cheapest s in [1, M / 512] whose slabs fit the workspace (s = 1 needs none).
+// Returns its cost, the split count in *s_out - or the per-layer cost with *s_out = 0 when the per-layer launches are cheaper.
+double tng_choose(const TnGroupShape* its, const double* layer_cost, int n, int M, long ws_floats, int ncu, int* s_out) {
+  double per_layer = 0.0;
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    per_layer += layer_cost[i];
+    tiles += tng_tiles(its[i]);
+  }
+  *s_out = 0;
+  if (n < 2 || ws_floats <= 0) return per_layer;
+  const long per_split = tng_slab_floats(its, n, 1);
+  const int smax = M / 512 > 0 ? M / 512 : 1;
+  double best = per_layer;
+  int last = 0;
+  for (int k = 1; k <= smax; ++k) {
+    int mps;
+    const int s = tng_splits(M, k, &mps);
+    if (s == last) continue;
+    last = s;
+    const long fl = s > 1 ? per_split * s : 0;
+    if (fl > ws_floats) break;
+    const double c = tng_cost(tiles, M, s, mps, fl, ncu);
+    if (c < best) {  // ties -> the per-layer path, then fewer splits
+      best = c;
+      *s_out = s;
+    }
+  }
+  return best;
+}
+
+// A run of n eligible items becomes one launch, or two: every cut of the list into a head and a tail (each a grouped launch
+// with its own split count, or per-layer) is priced, and a cut is taken when it is 3 % cheaper than the whole - at
+// 16384 x 1280 the 556 tiles are 2.17 rounds of the chip, and the first six layers at s = 1 (444 tiles, two rounds) plus the
+// last two at s = 2 beat every single split count.  Returns the cut position (n: none), the split counts in s[0], s[1].
+int tng_choose_cut(const TnGroupShape* its, int n, int M, long ws_floats, int* s) {
+  const int ncu = da_usable_cus(256);
+  double layer_cost[TN_GROUP_MAX];
+  for (int i = 0; i < n; ++i) layer_cost[i] = tng_layer_cost(its[i], M, ncu);
+  int cut = n;
+  s[1] = 0;
+  double best = tng_choose(its, layer_cost, n, M, ws_floats, ncu, &s[0]);
+  const double whole = best;
+  for (int k = 1; k < n; ++k) {
+    int sa, sb;
+    const double c = tng_choose(its, layer_cost, k, M, ws_floats, ncu, &sa) + tng_choose(its + k, layer_cost + k, n - k, M, ws_floats, ncu, &sb);
+    if (c < 0.97 * whole && c < best) {
+      best = c;
+      cut = k;
+      s[0] = sa;
+      s[1] = sb;
+    }
+  }
+  return cut;
+}
+
+bool tng_eligible(const DaWgradItem& it, int M) {
+  if (g_tn_ring || M % T2_MS || it.N < 8 || it.Cin < 8) return false;
+  if (64 * it.lddy >= (1L << 31) || 64 * it.ldx >= (1L << 31)) return false;
+  return da_tn_takes_v2(M, it.N, it.Cin);
+}
+
+int tng_launch(const DaWgradItem* items, const int* idx, int n, int M, int s, float* ws, hipStream_t stream) {
+  constexpr int SMEM = 2 * (T2_A_BYTES + T2_MS * 192 * 2);
+  TnGroupParams p;
+  p.n_items = n;
+  p.M = M;
+  p.splits = tng_splits(M, s, &p.m_per_split);
+  p.overwrite = g_grad_overwrite;
+  p.slab = ws;
+  long off = 0;
+  int first = 0, rfirst = 0, bfirst = 0;
+  for (int i = 0; i < n; ++i) {
+    const DaWgradItem& it = items[idx[i]];
+    TnGroupItem& g = p.it[i];
+    g.dY = (const bf16*)it.dY; g.X = (const bf16*)it.X; g.dW = it.dW; g.dbias = it.dbias;
+    g.lddy = (int)it.lddy; g.ldx = (int)it.ldx; g.N = it.N; g.Kt = it.Cin;
+    g.tiles_n = (it.N + T2_BN - 1) / T2_BN;
+    g.tiles_k = (it.Cin + 191) / 192;
+    g.first = first;
+    first += g.tiles_n * g.tiles_k * p.splits;
+    g.slab_off = off;
+    off += (long)g.tiles_n * p.splits * T2_BN * g.Kt;
+    g.bslab_off = off;
+    if (it.dbias) off += (long)g.tiles_n * p.splits * T2_BN;
+    long rb = ((long)g.N * (g.Kt >> 2) + 255) / 256;
+    if (rb > 2048) rb = 2048;
+    g.rfirst = rfirst; g.rblocks = (int)rb;
+    rfirst += (int)rb;
+    g.bfirst = bfirst;
+    if (it.dbias) bfirst += (g.N + 15) / 16;
+  }
+  for (int i = n; i < TN_GROUP_MAX; ++i) p.it[i] = p.it[0];
+  p.nblk = first;
+  static unsigned long long attr_ct = 0, attr_slab = 0;  // one bit per device
+  if (p.splits == 1) {
+    if (da_ensure_dyn_smem((const void*)gemm_tn2_group_kernel<true>, SMEM, &attr_ct) != DA_OK) return DA_ERR_LAUNCH;
+    hipLaunchKernelGGL(gemm_tn2_group_kernel<true>, dim3(p.nblk), dim3(512), SMEM, stream, p);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  }
+  if (da_ensure_dyn_smem((const void*)gemm_tn2_group_kernel<false>, SMEM, &attr_slab) != DA_OK) return DA_ERR_LAUNCH;
+  hipLaunchKernelGGL(gemm_tn2_group_kernel<false>, dim3(p.nblk), dim3(512), SMEM, stream, p);
+  DA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tn_group_reduce_kernel, dim3(rfirst + bfirst), dim3(256), 0, stream, p, rfirst);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// Walks the list: eligible items are collected, in order, into runs of up to TN_GROUP_MAX; each run becomes one or two
+// grouped launches with the split counts tng_choose_cut gives them, or - where that says so - is left to the per-layer path.
+// group_of[i] (may be null): the launch of item i, -1 = per-layer.  Returns the number of grouped launches, their split
+// counts in splits[0 .. cap).  With launch set, the grouped launches are enqueued (per-layer items are the caller's).
+int tng_plan(const DaWgradItem* items, int n_items, int M, long ws_floats, int* splits, int cap, int* group_of, bool launch, float* ws,
+             hipStream_t stream, int* rc) {
+  int ngroups = 0;
+  int idx[TN_GROUP_MAX];
+  TnGroupShape sh[TN_GROUP_MAX];
+  int n = 0;
+  if (group_of)
+    for (int i = 0; i < n_items; ++i) group_of[i] = -1;
+  for (int i = 0; i <= n_items; ++i) {
+    const bool el = i < n_items && !g_tn_ungroup && tng_eligible(items[i], M);
+    if (el) {
+      idx[n] = i;
+      sh[n] = TnGroupShape{items[i].N, items[i].Cin, items[i].dbias != nullptr};
+      ++n;
+    }
+    if (n == TN_GROUP_MAX || (i == n_items && n > 0)) {
+      int s2[2];
+      const int cut = tng_choose_cut(sh, n, M, ws_floats, s2);
+      for (int part = 0; part < 2; ++part) {
+        const int lo = part ? cut : 0, hi = part ? n : cut;
+        const int s = s2[part];
+        if (hi - lo < 2 || s <= 0) continue;
+        if (ngroups < cap && splits) splits[ngroups] = s;
+        if (group_of)
+          for (int j = lo; j < hi; ++j) group_of[idx[j]] = ngroups;
+        if (launch) {
+          const int r = tng_launch(items, idx + lo, hi - lo, M, s, ws, stream);
+          if (r != DA_OK) {
+            *rc = r;
+            return ngroups;
+          }
+        }
+        ++ngroups;
+      }
+      n = 0;
+    }
+  }
+  return ngroups;
+}
+
+int tng_validate(const DaWgradItem* items, int n_items, int M) {
+  if (n_items < 0 || (n_items > 0 && !items) || M <= 0 || M >= (1 << 24)) return DA_ERR_SHAPE;
+  for (int i = 0; i < n_items; ++i) {
+    const DaWgradItem& it = items[i];
+    if (it.N <= 0 || it.Cin <= 0 || (it.N & 7) || (it.Cin & 7) || (it.lddy & 7) || (it.ldx & 7)) return DA_ERR_SHAPE;
+    if (it.lddy < it.N || it.ldx < it.Cin) return DA_ERR_SHAPE;
+  }
+  return DA_OK;
+}
+
+}  // namespace
+
+extern "C" int da_gemm_tn_group_plan(const DaWgradItem* items, int n_items, int M, long split_ws_floats, int* splits, int cap,
+                                     int* group_of) {
+  if (tng_validate(items, n_items, M) != DA_OK || cap < 0) return -1;
+  int rc = DA_OK;
+  return tng_plan(items, n_items, M, split_ws_floats, splits, cap, group_of, false, nullptr, nullptr, &rc);
+}
+
+extern "C" int da_gemm_tn_wgrad_group(const DaWgradItem* items, int n_items, int M, float* split_ws, long split_ws_floats,
+                                      hipStream_t stream) {
+  DA_CLEAR_ERR();
+  if (tng_validate(items, n_items, M) != DA_OK) return DA_ERR_SHAPE;
+  if (!split_ws) split_ws_floats = 0;
+  // pointers are needed only by a launch: checked before anything is enqueued
+  for (int i = 0; i < n_items; ++i)
+    if (!items[i].dY || !items[i].X || !items[i].dW) return DA_ERR_SHAPE;
+  constexpr int CHUNK = 64;
+  for (int base = 0; base < n_items; base += CHUNK) {  // group_of lives on the stack: long lists in chunks of whole runs
+    const int n = n_items - base < CHUNK ? n_items - base : CHUNK;
+    int group_of[CHUNK];
+    int rc = DA_OK;
+    tng_plan(items + base, n, M, split_ws_floats, nullptr, 0, group_of, true, split_ws, stream, &rc);
+    if (rc != DA_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+      if (group_of[i] >= 0) continue;
+      const DaWgradItem& it = items[base + i];
+      // per-layer path, as da_gemm_tn_wgrad(..., ksize 1, mode 0); the small-shape kernel's bias column sum takes its
+      // scratch (256 * N * 2 floats) from the tail of the workspace
+      float* scratch = nullptr;
+      long wsf = split_ws_floats;
+      if (it.dbias && !da_tn_takes_v2(M, it.N, it.Cin)) {
+        const long need = 256L * it.N * 2;
+        if (wsf < need) return DA_ERR_SHAPE;
+        wsf -= need;
+        scratch = split_ws + wsf;
+      }
+      rc = da_gemm_tn_wgrad(it.dY, it.lddy, it.X, it.ldx, it.dW, it.dbias, scratch, M, it.N, it.Cin, 1, 1, 1, 1, 1, 0,
+                            wsf > 0 ? split_ws : nullptr, wsf, stream);
+      if (rc != DA_OK) return rc;
+    }
+  }
+  return DA_OK;
 }

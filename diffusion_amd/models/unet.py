@@ -296,6 +296,7 @@ class UNetHIP(nn.Module):
         self._grad_ready_cb = None  # parallel.BucketedAllReducer.ready during the last microbatch
         import os
         self.wgrad_stream = torch.cuda.Stream() if os.environ.get('DA_WGRAD_STREAM', '0') == '1' else None
+        self._wgrad_defer = None   # (M, [(dy, x, gw, dbias), ...]) while _transformer_bwd collects its linear weight gradients
         self._tape = None
         if init:
             self.reset_parameters(seed)
@@ -483,6 +484,10 @@ class UNetHIP(nn.Module):
         short-K dgrad kernels, which cannot use the matrix pipes) stop costing wall time of their own."""
         ws = self.wgrad_stream
         if ws is None:
+            d = self._wgrad_defer
+            if d is not None and g.ksize == 1 and g.mode == 0 and dy.shape[0] == d[0]:
+                d[1].append((dy, x, gw, dbias))   # a transformer block's linears: one grouped call at the end of the block
+                return
             ops.gemm_tn_wgrad(dy, x, gw, g, dbias=dbias, scratch=scratch)
             return
         main = torch.cuda.current_stream()
@@ -630,6 +635,18 @@ class UNetHIP(nn.Module):
         return y, saved
 
     def _transformer_bwd(self, saved, dout):
+        # The eight linear weight gradients over the block's M rows (nothing in the data-gradient chain reads them) are collected
+        # by _wgrad and run as ONE grouped call before the block returns: together they fill the chip with 1-13 pixel splits
+        # where each alone needs 9-125 (ops.gemm_tn_wgrad_group).  Their dY tensors stay alive until then.  attn2.kv
+        # (M = B * 77) and the side-stream form (wgrad_stream) keep the per-layer call.
+        if self.wgrad_stream is None:
+            self._wgrad_defer = (dout.shape[0], [])
+        try:
+            return self._transformer_bwd_chain(saved, dout)
+        finally:
+            self._wgrad_defer = None
+
+    def _transformer_bwd_chain(self, saved, dout):
         (p, x, gst, g, h0, ln1, n1, qkv, o1, l1, h1, ln2, n2, q2, kv2, o2, l2, h2, ln3, n3, f, gg, h3, B, H, W,
          heads) = saved
         HW = H * W
@@ -669,6 +686,10 @@ class UNetHIP(nn.Module):
         ops.gemm_nt(dqkv, mq.wt, dn1, Geom.linear(M))
         dh0 = self._ln_bwd(h0, dn1, dh1, tb + '.norm1', ln1)
         dg = self._lin_bwd(g, dh0, p + '.proj_in')
+        if self._wgrad_defer is not None:   # every gradient of the block is final when it returns (_grad_ready_cb contract)
+            items, self._wgrad_defer = self._wgrad_defer[1], None
+            ops.gemm_tn_wgrad_group(items, M)
+            del items
         return self._gn_bwd(x, dg, dout, p + '.norm', gst, B, HW, 0)
 
     # ------------------------------------------------------------------------------------------

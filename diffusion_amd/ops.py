@@ -236,6 +236,52 @@ def gemm_tn_wgrad(dY, X, dW, g: Geom, dbias=None, scratch=None):
                   SPLITK_WS.numel() if SPLITK_WS is not None else 0, _stream())
 
 
+def _wgrad_items(items, M):
+    """(dY, X, dW, dbias | None) per linear layer -> the DaWgradItem array of da_gemm_tn_wgrad_group, validated as
+    gemm_tn_wgrad validates one layer"""
+    arr = (_lib.DaWgradItem * max(len(items), 1))()
+    flops = 0.0
+    for i, (dY, X, dW, dbias) in enumerate(items):
+        dy_ptr, lddy = _mat(dY, BF16, f'items[{i}].dY')
+        x_ptr, ldx = _mat(X, BF16, f'items[{i}].X')
+        N, Cin = dY.shape[1], X.shape[1]
+        if dY.shape[0] != M or X.shape[0] != M:
+            raise ValueError(f'wgrad group: items[{i}] has {dY.shape[0]} / {X.shape[0]} rows, the group has {M}')
+        if dW.dtype != F32 or not dW.is_contiguous() or dW.numel() != N * Cin or not dW.is_cuda:
+            raise ValueError(f'items[{i}].dW must be contiguous fp32 with {N * Cin} elements on the device')
+        db = _vec(dbias, N, f'items[{i}].dbias') if dbias is not None else 0
+        arr[i] = _lib.DaWgradItem(dy_ptr, lddy, x_ptr, ldx, dW.data_ptr(), db or None, N, Cin)
+        flops += 2.0 * M * N * Cin
+    return arr, flops
+
+
+def gemm_tn_wgrad_group(items, M):
+    """The weight (and bias) gradients of several linear layers over the same M rows - items: (dY, X, dW, dbias | None) - as
+    grouped launches (da_gemm_tn_wgrad_group; the per-layer path for what is not eligible).  Recorded as ONE 'gemm_tn' entry
+    with the summed FLOPs, its time including the reduction."""
+    if not items:
+        return
+    arr, flops = _wgrad_items(items, M)
+    with _Timed('gemm_tn', flops, (M, len(items), 0, 1, 'group')):
+        _lib.call('da_gemm_tn_wgrad_group', arr, len(items), M, SPLITK_WS.data_ptr() if SPLITK_WS is not None else 0,
+                  SPLITK_WS.numel() if SPLITK_WS is not None else 0, _stream())
+
+
+def gemm_tn_group_plan(shapes, M, ws_floats):
+    """da_gemm_tn_group_plan (host only): shapes (N, Cin, has_dbias) -> {'splits': pixel splits of each grouped launch,
+    'group_of': launch of item i or -1 for the per-layer path}"""
+    n = len(shapes)
+    arr = (_lib.DaWgradItem * max(n, 1))()
+    for i, (N, Cin, has_db) in enumerate(shapes):
+        arr[i] = _lib.DaWgradItem(None, N, None, Cin, None, 1 if has_db else None, N, Cin)
+    splits = (ctypes.c_int * max(n, 1))()
+    group_of = (ctypes.c_int * max(n, 1))()
+    ng = _lib.load().da_gemm_tn_group_plan(arr, n, M, int(ws_floats), splits, n, group_of)
+    if ng < 0:
+        raise ValueError('da_gemm_tn_group_plan rejected the arguments')
+    return {'splits': list(splits[:ng]), 'group_of': list(group_of[:n])}
+
+
 def attn_fwd(Q, K, V, O, L2, B, H, Nq, Nk, scale):
     q, ldq = _mat(Q, BF16, 'Q')
     k, ldk = _mat(K, BF16, 'K')

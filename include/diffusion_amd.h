@@ -79,6 +79,8 @@ int da_gemm_nt_geglu_bwd(const void* dY, long lddy, const void* Wt, const void* 
  *   "gemm_nt_stream"    0 (default) | 1 / 2 the streaming short-K linear kernel (gemm_nt_v3.hip; slower) where it measured best /
  *                       wherever eligible; "gemm_nt_stream_lw" 4 | 16 its loader waves.  Bit-identical.
  *   "gemm_tn_ring"      0 (default) | 4 | 5: linear-layer weight gradients with a ring of 32-pixel half-stages (+-3 %).  Bit-identical.
+ *   "gemm_tn_ungroup"   0 (default) da_gemm_tn_wgrad_group runs eligible items as grouped launches | 1 every item through the
+ *                       per-layer path, one by one (the launches of da_gemm_tn_wgrad; A/B of the grouped form in one build)
  *   "attn_fused_bwd"    1 (default) da_attn_bwd runs as ONE kernel for Nk <= 128 (cross-attention, the 64-token level) | 0 the
  *                       dK/dV + dQ pair | 2 also 129 ... 256 keys on an 8-wave form (slower)
  *   "gemm_tn_variant"   0 auto | 1 the 128x128x32 wgrad kernel | 2 the 320x192x64 LDS-DMA wgrad kernel
@@ -115,6 +117,40 @@ int da_gemm_tn_wgrad(const void* dY, long lddy, const void* X, long ldx, float* 
 /* which kernel da_gemm_tn_wgrad dispatches to (test / profiling label): 1 = gemm_tn_kernel (128x128x32, register-staged),
  * 2 = gemm_tn2_kernel<192, generic gather>, 3 = gemm_tn2_kernel<192, FAST> (uniform source stride + periodic border mask) */
 int da_gemm_tn_variant_for(int M, int N, int Cin, int Hin, int Win, int Hout, int Wout, int ksize, int mode);
+
+/* One linear layer (ksize 1, mode 0) of a grouped weight gradient: dW[N][Cin] += dY[M][N]^T . X[M][Cin], and
+ * dbias[N] += column sums of dY when dbias != NULL.  lddy / ldx: row strides in elements. */
+typedef struct DaWgradItem {
+  const void* dY;
+  long lddy;
+  const void* X;
+  long ldx;
+  float* dW;
+  float* dbias;
+  int N;
+  int Cin;
+} DaWgradItem;
+
+/* The weight (and bias) gradients of n_items linear layers that share their row count M - the linears of one transformer
+ * block - with the contract of n_items da_gemm_tn_wgrad calls.  Items the 320x192x64 kernel takes on its FAST path
+ * (da_gemm_tn_variant_for == 3, M % 64 == 0) run, in list order and up to 16 at a time, as one or two launches whose
+ * workgroups cover the tiles of all their items: a layer alone has 2-28 tiles and needs 9-125 pixel splits to fill the chip,
+ * each storing a whole fp32 slab; together they need 1-13.  One split count per launch; it and the cut of a run into two
+ * launches are a pure function of the shapes (cost model in gemm_tn_v2.hip); with splits > 1 one reduce launch sums the
+ * slabs of all items in a fixed order, so dW and dbias are bitwise reproducible.  Same bf16 products, fp32 sums; only the summation order differs from the per-layer path.
+ * The per-layer path (bit-identical to da_gemm_tn_wgrad) takes: items that are not eligible, a run of fewer than two
+ * eligible items, every item when split_ws is NULL, and a run the cost model finds cheaper per layer (which includes a
+ * workspace too small for the split count worth having).  The small-shape kernel's bias column sum takes its scratch
+ * (256*N*2 floats) from the tail of split_ws: DA_ERR_SHAPE when such an item finds no room.  Nothing is allocated; the item
+ * table is copied into the kernel arguments, so the call may be captured into a graph. */
+int da_gemm_tn_wgrad_group(const DaWgradItem* items, int n_items, int M, float* split_ws, long split_ws_floats,
+                           da_stream_t stream);
+
+/* the plan of da_gemm_tn_wgrad_group for these shapes under the current options (host only; pointers in the items are not
+ * read except dbias != NULL): returns the number of grouped launches (-1: arguments the entry rejects), the pixel splits of
+ * launch g in splits[g] for g < cap, and, when group_of != NULL, group_of[i] = launch of item i or -1 for the per-layer path */
+int da_gemm_tn_group_plan(const DaWgradItem* items, int n_items, int M, long split_ws_floats, int* splits, int cap,
+                          int* group_of);
 
 /* softmax(Q K^T * scale) V for head_dim 64, heads at column offsets h*64 of Q/K/V/O; L2[B][H][Nq] receives the
  * per-row log2-sum-exp.  Replaces xformers memory_efficient_attention (models.py:109-111) / diffusers
