@@ -586,3 +586,158 @@ def test_resumable_loader_skips_at_index_level_and_reshuffles_per_epoch():
     dl.set_epoch(0, skip_batches=2)
     got = [x.tolist() for x in dl]
     assert got == [[10, 11, 12, 13, 14], [15, 16, 17, 18, 19]] and ds.loaded == list(range(10, 20))
+
+
+# ---- predicates of tests/test_pointwise_edges_gpu.py
+def _pointwise_edges():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_pointwise_edges_gpu as P
+    return P
+
+
+def test_pointwise_edge_rne_helper_rounds_once():
+    """rne_bf16 (float64 -> bf16 on the bit pattern) agrees with the fp32 -> bf16 conversion on every fp32 that is a bf16
+    value or exactly on a tie between two, denormals, +-0 and the overflow tie included; unlike a conversion through
+    fp32, it rounds a float64 just above a tie up."""
+    P = _pointwise_edges()
+    hi = torch.arange(65536, dtype=torch.int32)
+    hi = hi[((hi >> 7) & 0xFF) != 0xFF]
+    for low in (0x0000, 0x8000):                                   # the bf16 value itself; the tie above it (in magnitude)
+        x = ((hi << 16) | low).view(torch.float32)
+        assert torch.equal(P.rne_bf16(x.double()).view(torch.int16), x.to(torch.bfloat16).view(torch.int16)), hex(low)
+    x = torch.tensor([1.0 + 2.0 ** -8 + 2.0 ** -40, -(1.0 + 2.0 ** -8 + 2.0 ** -40), 1.0 + 2.0 ** -8, 2.0 ** -140,
+                      3.0e38, 3.4e38, float('inf'), -float('inf')], dtype=torch.float64)
+    want = torch.tensor([1.0 + 2.0 ** -7, -(1.0 + 2.0 ** -7), 1.0, 0.0, 3.0041e38, float('inf'), float('inf'),
+                         -float('inf')], dtype=torch.float64).to(torch.bfloat16)
+    assert torch.equal(P.rne_bf16(x), want), (P.rne_bf16(x), want)
+    assert float(x[0].to(torch.float32).to(torch.bfloat16)) == 1.0   # the double rounding the helper avoids
+    assert bool(torch.isnan(P.rne_bf16(torch.tensor([float('nan')], dtype=torch.float64))).all())
+    # needed_delta is the smallest delta the sandwich accepts: 0 for the rounded value, and just enough otherwise
+    r = torch.tensor([1.0 + 2.0 ** -9, 1.0 + 2.0 ** -9, -3.0], dtype=torch.float64)
+    out = torch.tensor([1.0, 1.0 + 2.0 ** -7, -3.0], dtype=torch.float64).to(torch.bfloat16)
+    need = P.needed_delta(out, r)
+    assert need.tolist() == [0.0, 2.0 ** -8 - 2.0 ** -9, 0.0]
+    assert bool(P.sandwich_ok(out, r, need * 1.001).all()) and not bool(P.sandwich_ok(out, r, need * 0.999)[1])
+
+
+def _emulated_formulas():
+    """common.hpp's activation formulas and quick-GELU in numpy fp32 (fmaf: one rounding of the float64 result)"""
+    import numpy as np
+    f = np.float32
+
+    def fma(a, b, c):
+        return (a.astype(np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f)
+
+    def sigmoid(x):
+        return f(1) / (f(1) + np.exp2(f(-1.4426950408889634) * x))
+
+    def silu(x):
+        return x * sigmoid(x)
+
+    def dsilu(x):
+        s = sigmoid(x)
+        return s * fma(x, f(1) - s, f(1))
+
+    def phi(x):
+        z = np.abs(x) * f(0.70710678118654752)
+        t = f(1) / fma(z, f(0.3275911), f(1))
+        poly = fma(t, f(1.061405429), f(-1.453152027))
+        for c in (1.421413741, -0.284496736, 0.254829592):
+            poly = fma(poly, t, f(c))
+        poly = poly * t
+        e = np.exp2(-(z * z) * f(1.4426950408889634))
+        er = np.copysign(fma(-poly, e, f(1)), x)
+        return fma(er, f(0.5), f(0.5)), e
+
+    def gelu(x):
+        return x * phi(x)[0]
+
+    def dgelu(x):
+        cdf, e = phi(x)
+        return fma(x * f(0.39894228040143268), e, cdf)
+
+    def qgelu(x):
+        return x / (f(1) + np.exp(f(-1.702) * x))
+
+    return {'silu': silu, 'dsilu': dsilu, 'gelu': gelu, 'dgelu': dgelu, 'qgelu': qgelu}
+
+
+def test_pointwise_edge_sandwich_accepts_the_fp32_formulas_and_rejects_other_functions():
+    """Over all 65,280 finite bf16 inputs the sandwich predicate, at HALF the delta the GPU module allows, accepts a numpy
+    fp32 emulation of each activation formula rounded to bf16; it rejects tanh-GELU and x * sigmoid(1.702 x) in place of
+    erf-GELU, and a sigmoid rounded to bf16 before the multiply - so it is sharp enough to tell functions apart.
+    quick-GELU's worst element is the same in the emulation and on the device (0.58783 of its unit), so a bound of twice
+    the device's figure, rounded down, leaves the emulation a factor 1.9999 instead of 2."""
+    import numpy as np
+    P = _pointwise_edges()
+    xb = P.all_finite_bf16()
+    x = xb.double()
+    xf = xb.float().numpy()
+    E = _emulated_formulas()
+    cases = {   # name: (float64 result, delta at the module's constants, slack)
+        'silu': (P.silu64(x), P.BOUNDS['silu.c'] * P.unit_silu(x), P.slack_sigmoid(x)),
+        'dsilu': (P.dsilu64(x), P.BOUNDS['dsilu.c'] * P.unit_dsilu(x), (1 + x.abs()) * P.TINY),
+        'qgelu': (P.qgelu64(x), P.BOUNDS['qgelu.c'] * P.unit_qgelu(x), P.slack_sigmoid(x)),
+        'gelu': (P.gelu64(x), P.delta_gelu(x), None),
+        'dgelu': (P.dgelu64(x), P.delta_gelu(x) / x.abs().clamp(min=1), None),
+    }
+    with np.errstate(all='ignore'):
+        for name, (r, delta, slack) in cases.items():
+            got32 = torch.from_numpy(E[name](xf))
+            assert not bool(torch.isnan(got32).any()), name
+            out = got32.to(torch.bfloat16)
+            ok = P.sandwich_ok(out, r, delta / (1.999 if name == 'qgelu' else 2) + (slack if slack is not None else 0))
+            assert bool(ok.all()), (name, int((~ok).sum()), xb[~ok][:4], out[~ok][:4], r[~ok][:4])
+            err = (got32.double() - r).abs()
+            if slack is not None:
+                err = (err - slack).clamp(min=0)
+            print(name, 'fp32 error / delta:', float((err / delta.clamp(min=1e-300))[delta > 0].max()),
+                  'smallest accepting delta / delta:', P.needed_c(out, r, delta, slack))
+        g = torch.from_numpy(E['gelu'](xf))
+        assert bool(P.gelu_exact_beyond_16(xb, g.to(torch.bfloat16)).all())
+        d = torch.from_numpy(E['dgelu'](xf)).double()
+        assert bool(((d == 1) | (x <= 16)).all()) and bool(((d == 0) | (x >= -16)).all())
+    tanh_gelu = 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
+    assert not bool(P.sandwich_ok(P.rne_bf16(tanh_gelu), P.gelu64(x), P.delta_gelu(x)).all())
+    assert not bool(P.sandwich_ok(P.rne_bf16(P.qgelu64(x)), P.gelu64(x), P.delta_gelu(x)).all())
+    early = x * P.rne_bf16(torch.sigmoid(x)).double()
+    assert not bool(P.sandwich_ok(P.rne_bf16(early), P.silu64(x),
+                                  P.BOUNDS['silu.c'] * P.unit_silu(x) + P.slack_sigmoid(x)).all())
+
+
+def test_pointwise_edge_transposed_weight_reference_is_the_dgrad_weight():
+    """src.view(N, T, C).permute(2, 1, 0).flip(1) - the reference of the weight-shadow tests - is, for T = 9, the weight
+    with which a 3x3 convolution over dY gives the input gradient (the flipped-kernel identity), in float64"""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(5)
+    N, C, B, H, W = 6, 4, 2, 5, 3
+    w = torch.randn(N, C, 3, 3, generator=g, dtype=torch.float64)           # conv weight [out, in, r, s]
+    dy = torch.randn(B, N, H, W, generator=g, dtype=torch.float64)
+    src = w.permute(0, 2, 3, 1).reshape(N, 9, C)                            # kernel layout [N][T][C]
+    dst = src.view(N, 9, C).permute(2, 1, 0).flip(1)                        # [C][T][N]
+    wt = dst.reshape(C, 3, 3, N).permute(0, 3, 1, 2)                        # back to [out = C, in = N, r, s]
+    assert torch.allclose(F.conv2d(dy, wt, padding=1), F.conv_transpose2d(dy, w, padding=1), rtol=0, atol=1e-12)
+    x = torch.randn(B, C, H, W, generator=g, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w, padding=1).backward(dy)
+    assert torch.allclose(F.conv2d(dy, wt, padding=1), x.grad, rtol=0, atol=1e-12)
+
+
+def test_pointwise_edge_batched_tables_cover_both_paths_and_ragged_tiles():
+    """the descriptor tables of the batched weight-shadow test: T = 1 and 9, N and C of 8, 64, 72, 320 and 1280 (ragged
+    64-tiles), and the scalar path by C = 4 and by N = 12; total_blocks follows refresh_transposed's formula"""
+    P = _pointwise_edges()
+    assert sorted(P.BATCHED_TABLES) == [1, 2, 3, 5, 8] and all(len(v) == k for k, v in P.BATCHED_TABLES.items())
+    tensors = [t for table in P.BATCHED_TABLES.values() for t in table]
+    assert {t[1] for t in tensors} == {1, 9}
+    assert {8, 64, 72, 320, 1280} <= {t[0] for t in tensors} and {8, 64, 72, 320, 1280} <= {t[2] for t in tensors}
+    assert any(t[2] == 4 for t in tensors) and any(t[0] == 12 for t in tensors)
+    for table in P.BATCHED_TABLES.values():
+        desc, rows, total, ns, nd = P.batched_layout(table)
+        assert len(desc) == 32 * len(table)
+        assert total == sum(T * ((N + 63) // 64) * ((C + 63) // 64) for N, T, C in table)
+        assert [r[5] for r in rows] == sorted(r[5] for r in rows) and rows[0][5] == 0
+        assert all(r[0] % 8 == 0 and r[1] % 8 == 0 for r in rows)
+        assert all(rows[i][1] + rows[i][2] * rows[i][3] * rows[i][4] + P.GAP <= rows[i + 1][1] for i in range(len(rows) - 1))
+        shifted = P.batched_layout(table, shift_tensor=0, shift=4)[1]
+        assert shifted[0][0] % 8 == 4 and shifted[0][1] % 8 == 4
