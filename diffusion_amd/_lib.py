@@ -35,6 +35,7 @@ SIGNATURES = {
     'da_gemm_tn_group_plan': [C.POINTER(DaWgradItem), _i, _i, _l, C.POINTER(_i), _i, C.POINTER(_i)],
     'da_attn_fwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _i, _i, _i, _i, _f, _vp],
     'da_attn_fwd_causal': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _i, _i, _i, _f, _vp],
+    'da_attn_fwd_wide': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _i, _i, _i, _i, _i, _f, _vp],
     'da_attn_bwd': [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _fp, _fp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i,
                     _f, _vp],
     'da_norm_scratch_floats': [_i, _i, _i],

@@ -115,7 +115,7 @@ def stable_diffusion_2(
 
     if build_encoders is None:
         build_encoders = not precomputed_latents
-    vae = text_encoder = vae_hip = text_hip = None
+    vae = text_encoder = vae_hip = vae_dec_hip = text_hip = None
     from .text import build_text_encoder, build_tokenizer
     tokenizer = build_tokenizer(os.path.join(local, 'tokenizer') if local else None)
     if build_encoders:
@@ -133,16 +133,17 @@ def stable_diffusion_2(
                           'tests, meaningless for real training with precomputed_latents=False or for generate()')
         if pretrained and not (te_dir and os.path.isdir(te_dir)):
             raise FileNotFoundError(f'pretrained=True but {te_dir} is missing: the frozen text encoder would be random')
-        vae_hip = None
         # The HIP encoders compute in bf16 (activations and residual stream), i.e. at the precision class the caller asked
         # for with encode_latents_in_fp16=True (the reference default, models.py:37).  With encode_latents_in_fp16=False
         # the reference encodes the training targets in fp32: then the PyTorch-ROCm fp32 modules run unless the HIP
         # encoders are asked for explicitly (DA_VAE_HIP=1 / DA_TEXT_HIP=1).
         hip_default = '1' if encode_latents_in_fp16 else '0'
         if os.environ.get('DA_VAE_HIP', hip_default) != '0':
-            # the encoder half of the frozen VAE on the HIP kernels (models/vae_hip.py), built from the fp32 weights
-            from .vae_hip import VAEEncoderHIP
+            # both halves of the frozen VAE on the HIP kernels (models/vae_hip.py), built from the fp32 weights: the encoder
+            # for the training step, the decoder for generate()
+            from .vae_hip import VAEDecoderHIP, VAEEncoderHIP
             vae_hip = VAEEncoderHIP(vae.to('cuda'))
+            vae_dec_hip = VAEDecoderHIP(vae)
         vae = vae.to('cuda', dtype)
         text_encoder = build_text_encoder(te_dir, torch.float32, hidden_size=unet_config.cross_attention_dim).to('cuda')
         text_hip = None
@@ -172,6 +173,7 @@ def stable_diffusion_2(
         fsdp=fsdp,
     )
     model.vae_hip = vae_hip if build_encoders else None
+    model.vae_dec_hip = vae_dec_hip if build_encoders else None
     model.text_hip = text_hip if build_encoders else None
     return model
 

@@ -321,8 +321,14 @@ class StableDiffusion(ComposerModel):
                 pred = pu + guidance_scale * (pt - pu)
             latents = self.inference_scheduler.step(pred, t, latents, generator=rng)['prev_sample']
         latents = 1 / 0.18215 * latents
-        vdtype = next(self.vae.parameters()).dtype
-        image = self.vae.decode(latents.to(vdtype)).sample
+        # image decoder: the HIP-kernel walk of the same frozen weights when the factory built one (models/vae_hip.py),
+        # else the PyTorch-ROCm module
+        vae_dec_hip = getattr(self, 'vae_dec_hip', None)
+        if vae_dec_hip is not None:
+            image = vae_dec_hip.decode(latents).sample
+        else:
+            vdtype = next(self.vae.parameters()).dtype
+            image = self.vae.decode(latents.to(vdtype)).sample
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.detach().float()
 

@@ -1,18 +1,20 @@
-"""Frozen SD-2 VAE ENCODER on the hand-written gfx950 kernels (forward only).
+"""Frozen SD-2 VAE on the hand-written gfx950 kernels (forward only): ``VAEEncoderHIP`` and ``VAEDecoderHIP``.
 
 The reference encodes images inside the training step when latents are not precomputed
 (/root/reference diffusion/models/stable_diffusion.py:160-174: ``vae.encode(x)['latent_dist'].sample()`` then
-``*= 0.18215``) and prices that at x1.4 step time (README.md:52).  On PyTorch-ROCm the fp16 encoder alone costs twice
-the whole U-Net training step per image (466 vs 1,390 images/s); its arithmetic is the same op set the U-Net
-kernels already cover - GroupNorm(32, eps 1e-6)+SiLU, 3x3 / 1x1 convolutions on NHWC bf16, one stride-2 downsampler per
-level - so this module walks the encoder of ``models/vae.AutoencoderKL`` through ``da_groupnorm_fwd`` / ``da_gemm_nt``
-(gather mode 4 = Downsample2D's bottom/right zero padding).  Only the single 512-wide mid-block attention head
-(1,024 tokens at 256 px; the flash kernels are specialised for head_dim 64) stays on torch SDPA.
+``*= 0.18215``) and prices that at x1.4 step time (README.md:52), and decodes sampled latents in ``generate``
+(:380 ``vae.decode(latents).sample``).  On PyTorch-ROCm the fp16 encoder alone costs twice the whole U-Net training step per
+image (466 vs 1,390 images/s); the VAE's arithmetic is the op set the U-Net kernels already cover -
+GroupNorm(32, eps 1e-6)+SiLU, 3x3 / 1x1 convolutions on NHWC bf16, one stride-2 downsampler (gather mode 4 = Downsample2D's
+bottom/right zero padding) or one nearest-2x upsampler convolution (gather mode 3, no materialised upsampled tensor) per
+level - so this module walks ``models/vae.AutoencoderKL`` through ``da_groupnorm_fwd`` / ``da_gemm_nt``.  The single
+512-wide mid-block attention head (1,024 tokens at 256 px) runs on ``da_attn_fwd_wide``; only an ``AutoencoderKL`` built
+with another mid width falls to torch SDPA for that one product.
 
-Weights are taken from the torch module (bf16 OHWI copies; ``quant_conv`` is folded into ``conv_out``); activations are
-bf16 with fp32 accumulation / statistics where the reference runs the encoder in fp16 (``encode_latents_in_fp16``):
-tests/test_vae_hip_gpu.py bounds the difference of the latent moments against the fp32 torch encoder.
-The decoder (only used by ``generate``) stays on PyTorch-ROCm.
+Weights are taken from the torch module (bf16 OHWI copies; the encoder folds ``quant_conv`` into ``conv_out``; the decoder
+runs ``post_quant_conv`` as its own 1x1 GEMM because ``conv_in`` zero-pads the BIASED tensor); activations are bf16 with
+fp32 accumulation / statistics where the reference runs the VAE in fp16 (``encode_latents_in_fp16``):
+tests/test_vae_hip_gpu.py and tests/test_vae_decoder_hip_gpu.py bound the differences against the fp32 torch module.
 """
 from __future__ import annotations
 
@@ -35,67 +37,51 @@ def _ohwi(w: torch.Tensor, cin_pad: int = 0, cout_pad: int = 0) -> torch.Tensor:
     return t.reshape(op, kh * kw * ip).to(BF16).contiguous()
 
 
-class VAEEncoderHIP:
-    """``encode(images)`` -> the same ``{'latent_dist': DiagonalGaussian}`` as ``AutoencoderKL.encode``."""
+class _VAEWalkHIP:
+    """What the two halves share: weight preparation from the torch module's state dict under ``prefix``, the
+    GroupNorm / resnet / mid-block walks and their buffers."""
+    name = '_VAEWalkHIP'
 
-    def __init__(self, vae: AutoencoderKL, device='cuda'):
+    def __init__(self, vae: AutoencoderKL, prefix: str, device='cuda'):
         self.dev = torch.device(device)
         if self.dev.type != 'cuda':
-            raise RuntimeError('VAEEncoderHIP runs on an MI355X only')
+            raise RuntimeError(f'{self.name} runs on an MI355X only')
         self.w: Dict[str, torch.Tensor] = {}
         self.v: Dict[str, torch.Tensor] = {}
-        enc = vae.encoder
-        sd = {k: v.detach().to(self.dev, torch.float32) for k, v in vae.state_dict().items()}
+        self.prefix = prefix
+        self.sd = {k: v.detach().to(self.dev, torch.float32) for k, v in vae.state_dict().items()}
+        self._scratch = None
 
-        def conv(key, cin_pad=0, cout_pad=0):
-            self.w[key] = _ohwi(sd[f'encoder.{key}.weight'], cin_pad, cout_pad)
-            b = sd[f'encoder.{key}.bias']
-            self.v[key + '.bias'] = F.pad(b, (0, max(0, cout_pad - b.numel()))).contiguous()
+    def _conv(self, key, cin_pad=0, cout_pad=0, prefix=None):
+        prefix = self.prefix if prefix is None else prefix
+        self.w[key] = _ohwi(self.sd[f'{prefix}{key}.weight'], cin_pad, cout_pad)
+        b = self.sd[f'{prefix}{key}.bias']
+        self.v[key + '.bias'] = F.pad(b, (0, max(0, cout_pad - b.numel()))).contiguous()
 
-        def norm(key):
-            self.v[key + '.weight'] = sd[f'encoder.{key}.weight'].contiguous()
-            self.v[key + '.bias'] = sd[f'encoder.{key}.bias'].contiguous()
+    def _norm(self, key):
+        self.v[key + '.weight'] = self.sd[f'{self.prefix}{key}.weight'].contiguous()
+        self.v[key + '.bias'] = self.sd[f'{self.prefix}{key}.bias'].contiguous()
 
-        def lin(key):
-            self.w[key] = sd[f'encoder.{key}.weight'].to(BF16).contiguous()
-            self.v[key + '.bias'] = sd[f'encoder.{key}.bias'].contiguous()
+    def _lin(self, key):
+        self.w[key] = self.sd[f'{self.prefix}{key}.weight'].to(BF16).contiguous()
+        self.v[key + '.bias'] = self.sd[f'{self.prefix}{key}.bias'].contiguous()
 
-        def res(key, cin, cout):
-            norm(key + '.norm1'); conv(key + '.conv1'); norm(key + '.norm2'); conv(key + '.conv2')
-            if cin != cout:
-                conv(key + '.conv_shortcut')
+    def _prep_res(self, key, cin, cout):
+        self._norm(key + '.norm1'); self._conv(key + '.conv1'); self._norm(key + '.norm2'); self._conv(key + '.conv2')
+        if cin != cout:
+            self._conv(key + '.conv_shortcut')
 
-        conv('conv_in', cin_pad=8)
-        self.levels = []
-        cin = enc.conv_in.out_channels
-        for i, blk in enumerate(enc.down_blocks):
-            cout = blk.resnets[0].conv1.out_channels
-            res(f'down_blocks.{i}.resnets.0', cin, cout)
-            res(f'down_blocks.{i}.resnets.1', cout, cout)
-            down = blk.downsamplers is not None
-            if down:
-                conv(f'down_blocks.{i}.downsamplers.0.conv')
-            self.levels.append((cin, cout, down))
-            cin = cout
-        self.cmid = cin
-        res('mid_block.resnets.0', cin, cin)
-        res('mid_block.resnets.1', cin, cin)
-        norm('mid_block.attentions.0.group_norm')
+    def _prep_mid(self, c):
+        self.cmid = c
+        self._prep_res('mid_block.resnets.0', c, c)
+        self._prep_res('mid_block.resnets.1', c, c)
+        self._norm('mid_block.attentions.0.group_norm')
         for n in ('to_q', 'to_k', 'to_v', 'to_out.0'):
-            lin(f'mid_block.attentions.0.{n}')
+            self._lin(f'mid_block.attentions.0.{n}')
         # fused q|k|v projection
         a = 'mid_block.attentions.0'
         self.w[a + '.qkv'] = torch.cat([self.w[f'{a}.to_q'], self.w[f'{a}.to_k'], self.w[f'{a}.to_v']]).contiguous()
         self.v[a + '.qkv.bias'] = torch.cat([self.v[f'{a}.to_q.bias'], self.v[f'{a}.to_k.bias'], self.v[f'{a}.to_v.bias']])
-        norm('conv_norm_out')
-        # conv_out (3x3, C -> 2z) followed by quant_conv (1x1, 2z -> 2z): one 3x3 conv with composed weights
-        wo, bo = sd['encoder.conv_out.weight'], sd['encoder.conv_out.bias']
-        wq, bq = sd['quant_conv.weight'][:, :, 0, 0], sd['quant_conv.bias']
-        self.w['conv_out'] = _ohwi(torch.einsum('pq,qikl->pikl', wq, wo))
-        self.v['conv_out.bias'] = (wq @ bo + bq).contiguous()
-        self.zc2 = wo.shape[0]
-        self._scratch = None
-        self._skey = None
 
     # ------------------------------------------------------------------------------------------
     def _bf(self, m, c):
@@ -134,6 +120,56 @@ class VAEEncoderHIP:
         ops.gemm_nt(a, self.w[key + '.conv2'], y, g3, bias=self.v[key + '.conv2.bias'], residual=x)
         return y
 
+    def _mid(self, h, B, H, W):
+        """resnet, single-head attention over the H*W tokens, resnet"""
+        h = self._res('mid_block.resnets.0', h, B, H, W)
+        a = 'mid_block.attentions.0'
+        Cm, N = self.cmid, H * W
+        g = self._gn(h, a + '.group_norm', B, N, 0)
+        qkv = self._bf(B * N, 3 * Cm)
+        ops.gemm_nt(g, self.w[a + '.qkv'], qkv, Geom.linear(B * N), bias=self.v[a + '.qkv.bias'])
+        if Cm == 512:
+            # head_dim = C = 512: the three column slices of the fused buffer go to the kernel as strided views
+            o = self._bf(B * N, Cm)
+            l2 = torch.empty(B * N, device=self.dev, dtype=F32)
+            ops.attn_fwd_wide(qkv[:, :Cm], qkv[:, Cm:2 * Cm], qkv[:, 2 * Cm:], o, l2, B, 1, Cm, N, N, Cm**-0.5)
+        else:   # an AutoencoderKL with another mid width: no kernel for that head_dim
+            q, k, v = (qkv[:, j * Cm:(j + 1) * Cm].reshape(B, 1, N, Cm) for j in range(3))
+            o = F.scaled_dot_product_attention(q, k, v).reshape(B * N, Cm).contiguous()
+        y = self._bf(B * N, Cm)
+        ops.gemm_nt(o, self.w[a + '.to_out.0'], y, Geom.linear(B * N), bias=self.v[a + '.to_out.0.bias'], residual=h)
+        return self._res('mid_block.resnets.1', y, B, H, W)
+
+
+class VAEEncoderHIP(_VAEWalkHIP):
+    """``encode(images)`` -> the same ``{'latent_dist': DiagonalGaussian}`` as ``AutoencoderKL.encode``."""
+    name = 'VAEEncoderHIP'
+
+    def __init__(self, vae: AutoencoderKL, device='cuda'):
+        super().__init__(vae, 'encoder.', device)
+        enc = vae.encoder
+        self._conv('conv_in', cin_pad=8)
+        self.levels = []
+        cin = enc.conv_in.out_channels
+        for i, blk in enumerate(enc.down_blocks):
+            cout = blk.resnets[0].conv1.out_channels
+            self._prep_res(f'down_blocks.{i}.resnets.0', cin, cout)
+            self._prep_res(f'down_blocks.{i}.resnets.1', cout, cout)
+            down = blk.downsamplers is not None
+            if down:
+                self._conv(f'down_blocks.{i}.downsamplers.0.conv')
+            self.levels.append((cin, cout, down))
+            cin = cout
+        self._prep_mid(cin)
+        self._norm('conv_norm_out')
+        # conv_out (3x3, C -> 2z) followed by quant_conv (1x1, 2z -> 2z): one 3x3 conv with composed weights
+        wo, bo = self.sd['encoder.conv_out.weight'], self.sd['encoder.conv_out.bias']
+        wq, bq = self.sd['quant_conv.weight'][:, :, 0, 0], self.sd['quant_conv.bias']
+        self.w['conv_out'] = _ohwi(torch.einsum('pq,qikl->pikl', wq, wo))
+        self.v['conv_out.bias'] = (wq @ bo + bq).contiguous()
+        self.zc2 = wo.shape[0]
+        del self.sd
+
     @torch.no_grad()
     def moments(self, images: torch.Tensor) -> torch.Tensor:
         """images [B,3,H,W] (any float dtype, NCHW) -> [B, 2*z, H/8, W/8] fp32 (mean | logvar)."""
@@ -153,18 +189,8 @@ class VAEEncoderHIP:
                 y = self._bf(B * (H // 2) * (W // 2), cout)
                 ops.gemm_nt(h, self.w[key], y, Geom.down_vae(B, H, W), bias=self.v[key + '.bias'])
                 h, H, W = y, H // 2, W // 2
-        h = self._res('mid_block.resnets.0', h, B, H, W)
-        # single-head attention over the H*W tokens (head_dim = C = 512: torch SDPA; projections on the HIP GEMM)
-        a = 'mid_block.attentions.0'
-        Cm, N = self.cmid, H * W
-        g = self._gn(h, a + '.group_norm', B, N, 0)
-        qkv = self._bf(B * N, 3 * Cm)
-        ops.gemm_nt(g, self.w[a + '.qkv'], qkv, Geom.linear(B * N), bias=self.v[a + '.qkv.bias'])
-        q, k, v = (qkv[:, j * Cm:(j + 1) * Cm].reshape(B, 1, N, Cm) for j in range(3))
-        o = F.scaled_dot_product_attention(q, k, v).reshape(B * N, Cm).contiguous()
-        y = self._bf(B * N, Cm)
-        ops.gemm_nt(o, self.w[a + '.to_out.0'], y, Geom.linear(B * N), bias=self.v[a + '.to_out.0.bias'], residual=h)
-        h = self._res('mid_block.resnets.1', y, B, H, W)
+        h = self._mid(h, B, H, W)
+        N = H * W
         g = self._gn(h, 'conv_norm_out', B, N, 1)
         out = torch.empty(B * N, self.zc2, device=self.dev, dtype=F32)
         ops.gemm_nt(g, self.w['conv_out'], out, Geom.conv(B, H, W), bias=self.v['conv_out.bias'])
@@ -172,3 +198,59 @@ class VAEEncoderHIP:
 
     def encode(self, images: torch.Tensor):
         return _Out(latent_dist=DiagonalGaussian(self.moments(images)))
+
+
+class VAEDecoderHIP(_VAEWalkHIP):
+    """``decode(z)`` -> the same ``{'sample': images}`` as ``AutoencoderKL.decode`` (fp32, NCHW)."""
+    name = 'VAEDecoderHIP'
+
+    def __init__(self, vae: AutoencoderKL, device='cuda'):
+        super().__init__(vae, 'decoder.', device)
+        dec = vae.decoder
+        # post_quant_conv (1x1, z -> z) stays a GEMM of its own: conv_in zero-pads its BIASED output, so composing the two
+        # would change the border pixels.  Its 4 output channels are padded to the 8 that conv_in reads (zero rows / bias).
+        self._conv('post_quant_conv', cin_pad=8, cout_pad=8, prefix='')
+        self._conv('conv_in', cin_pad=8)
+        cin = dec.conv_in.out_channels
+        self._prep_mid(cin)
+        self.levels = []
+        for i, blk in enumerate(dec.up_blocks):
+            cout = blk.resnets[0].conv1.out_channels
+            for j in range(len(blk.resnets)):
+                self._prep_res(f'up_blocks.{i}.resnets.{j}', cin if j == 0 else cout, cout)
+            up = blk.upsamplers is not None
+            if up:
+                self._conv(f'up_blocks.{i}.upsamplers.0.conv')
+            self.levels.append((len(blk.resnets), cout, up))
+            cin = cout
+        self._norm('conv_norm_out')
+        self._conv('conv_out', cout_pad=8)
+        self.zc = dec.conv_in.in_channels
+        self.out_channels = dec.conv_out.out_channels
+        del self.sd
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor):
+        """z [B,zc,h,w] (any float dtype, NCHW) -> ``sample`` [B,3,8h,8w] fp32"""
+        B, C, H, W = z.shape
+        if C != self.zc:
+            raise ValueError(f'VAEDecoderHIP: latents must be [B,{self.zc},h,w]')
+        x = torch.zeros(B * H * W, 8, device=self.dev, dtype=BF16)   # NHWC, latent channels padded to 8
+        x.view(B, H, W, 8)[..., :C] = z.to(self.dev).permute(0, 2, 3, 1)
+        zq = self._bf(B * H * W, 8)
+        ops.gemm_nt(x, self.w['post_quant_conv'], zq, Geom.conv(B, H, W, 1), bias=self.v['post_quant_conv.bias'])
+        h = self._bf(B * H * W, self.w['conv_in'].shape[0])
+        ops.gemm_nt(zq, self.w['conv_in'], h, Geom.conv(B, H, W), bias=self.v['conv_in.bias'])
+        h = self._mid(h, B, H, W)
+        for i, (nres, cout, up) in enumerate(self.levels):
+            for j in range(nres):
+                h = self._res(f'up_blocks.{i}.resnets.{j}', h, B, H, W)
+            if up:   # the 3x3 conv reads the nearest-2x upsampled image through the gather: no upsampled tensor
+                key = f'up_blocks.{i}.upsamplers.0.conv'
+                y = self._bf(B * 4 * H * W, cout)
+                ops.gemm_nt(h, self.w[key], y, Geom.up(B, H, W), bias=self.v[key + '.bias'])
+                h, H, W = y, 2 * H, 2 * W
+        g = self._gn(h, 'conv_norm_out', B, H * W, 1)
+        out = torch.empty(B * H * W, 8, device=self.dev, dtype=F32)
+        ops.gemm_nt(g, self.w['conv_out'], out, Geom.conv(B, H, W), bias=self.v['conv_out.bias'])
+        return _Out(sample=out.view(B, H, W, 8)[..., :self.out_channels].permute(0, 3, 1, 2))

@@ -295,6 +295,20 @@ def attn_fwd(Q, K, V, O, L2, B, H, Nq, Nk, scale):
                   float(scale), _stream())
 
 
+def attn_fwd_wide(Q, K, V, O, L2, B, H, D, Nq, Nk, scale):
+    """da_attn_fwd for head_dim D = 512 (the VAE's single mid-block head), forward only; same operand layout"""
+    q, ldq = _mat(Q, BF16, 'Q')
+    k, ldk = _mat(K, BF16, 'K')
+    v, ldv = _mat(V, BF16, 'V')
+    o, ldo = _mat(O, BF16, 'O')
+    for t, n in ((Q, Nq), (O, Nq), (K, Nk), (V, Nk)):
+        if tuple(t.shape) != (B * n, H * D):
+            raise ValueError(f'attention operand shape {tuple(t.shape)} != {(B * n, H * D)}')
+    with _Timed('attn_fwd_wide', 4.0 * B * H * Nq * Nk * D, (B, H, Nq, Nk, D)):
+        _lib.call('da_attn_fwd_wide', q, ldq, k, ldk, v, ldv, o, ldo, _f32buf(L2, B * H * Nq, 'L2'), B, H, D, Nq, Nk,
+                  float(scale), _stream())
+
+
 def attn_fwd_causal(Q, K, V, O, L2, B, H, N, scale):
     """causal self-attention (key j <= query q), forward only: the frozen text encoder"""
     q, ldq = _mat(Q, BF16, 'Q')

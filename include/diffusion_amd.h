@@ -161,6 +161,11 @@ int da_attn_fwd(const void* Q, long ldq, const void* K, long ldk, const void* V,
  * (transformers CLIPTextModel behind stable_diffusion.py:168,172); forward only. */
 int da_attn_fwd_causal(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
                        float* L2, int B, int H, int N, float scale, da_stream_t stream);
+/* the forward for head_dim D = 512 (the only D accepted; heads at column offsets h*D, every ld a multiple of 8 and >= H*D,
+ * else DA_ERR_SHAPE with nothing launched): the single mid-block attention head of the frozen VAE, encoder and decoder
+ * (diffusers AutoencoderKL behind stable_diffusion.py:167,171 `vae.encode` and :380 `vae.decode`); forward only. */
+int da_attn_fwd_wide(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
+                     float* L2, int B, int H, int D, int Nq, int Nk, float scale, da_stream_t stream);
 /* backward of da_attn_fwd; Delta[B][H][Nq] is scratch (rowsum(dO*O)). */
 int da_attn_bwd(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, const void* O, long ldo,
                 const void* dO, long lddo, const float* L2, float* Delta, void* dQ, long lddq, void* dK, long lddk,
