@@ -1,0 +1,142 @@
+// Raw-image ingest: LargestCenterSquare(R) + ToTensor + Normalize(0.5, 0.5) of packed RGB uint8 images, i.e. PIL's
+// antialiased bilinear resize of the shorter side to R followed by the centre crop, written straight into the layout the
+// VAE encoder's conv_in reads (NHWC-8 bf16) or into the reference's fp32 NCHW `image` tensor.
+//
+// Arithmetic.  Along one axis (n_in source samples -> n_out resized samples, M = max(n_in, n_out)) output index i has its
+// filter centre at c = (i + 0.5) n_in / n_out and the tap at source index x weighs 1 - |x - c + 0.5| / max(n_in/n_out, 1).
+// With num = 2 n_out x + n_out - (2 i + 1) n_in that weight is (2M - |num|) / 2M: an INTEGER numerator W over a constant
+// that the normalisation cancels.  So the weights are kept as exact integers, the tap window [lo, hi) comes from integer
+// divisions (no float centre that loses bits at index 4000 of a 60000-pixel axis), the sums run in fp64 and are divided by
+// the integer weight sum: a constant image comes out as exactly that constant (partition of unity holds at the borders,
+// where the window is clipped), and every other value carries two fp32 roundings - the row cache and the output.
+//
+// Staging.  One 256-thread block owns a 16x16 tile of the cropped output of one image.  The source rows the tile needs are
+// walked in chunks of 16: thread (r, x) filters source row v0 + r horizontally for output column x (3 channels, byte loads,
+// nothing wider: an image may start at any byte address) into a 16x16x3 fp32 row cache in LDS; after a barrier thread
+// (y, x) adds the rows of the chunk that fall into its vertical window.  Tap counts are loop bounds, not array sizes.
+// The horizontal pass is shared by the 16 rows of the tile; vertically adjacent tiles repeat the rows their windows share
+// ((16 + 2) / 16 of the minimum when downscaling).  Every read is at row lo..hi-1 < h, column lo..hi-1 < w of its own image.
+#include "common.hpp"
+#include "diffusion_amd.h"
+
+namespace {
+
+constexpr int IMG_TILE = 16;       // output tile side; block = IMG_TILE^2 threads
+constexpr int IMG_MAX_SIDE = 65535;  // sides above this are skipped (nothing written): keeps every numerator inside int32 / int64
+
+// the taps of output index i (in the resized, uncropped axis): window [lo, hi), numerator of the first tap, 1 / sum of W
+DEVINL void axis_setup(int n_in, int n_out, int i, int* lo_, int* hi_, int* num_, double* inv_) {
+  const long long M2 = 2LL * (n_in > n_out ? n_in : n_out), ci = (2LL * i + 1) * n_in;
+  const long long a_lo = ci - M2 + n_out, a_hi = ci + M2 + n_out;
+  long long lo = a_lo > 0 ? a_lo / (2LL * n_out) : 0;   // int(c - fs + 0.5) clipped at 0
+  long long hi = a_hi / (2LL * n_out);                  // int(c + fs + 0.5) clipped at n_in
+  if (hi > n_in) hi = n_in;
+  if (lo > hi) lo = hi;
+  const int num0 = (int)(2LL * n_out * lo + n_out - ci);
+  long long sum = 0;
+  int num = num0;
+  for (int x = (int)lo; x < (int)hi; ++x, num += 2 * n_out) {
+    const int W = (int)M2 - abs(num);
+    sum += W > 0 ? W : 0;
+  }
+  *lo_ = (int)lo;
+  *hi_ = (int)hi;
+  *num_ = num0;
+  *inv_ = sum > 0 ? 1.0 / (double)sum : 0.0;
+}
+
+__global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const unsigned char* __restrict__ src,
+                                                                          const long long* __restrict__ off,
+                                                                          const int* __restrict__ hw, int R, int tiles,
+                                                                          void* __restrict__ out, int kind) {
+  __shared__ int s_lo[2][IMG_TILE], s_hi[2][IMG_TILE], s_num[2][IMG_TILE];
+  __shared__ double s_inv[2][IMG_TILE];
+  __shared__ float s_row[IMG_TILE][IMG_TILE][3];
+  const int t = threadIdx.x;
+  const int b = blockIdx.x / (tiles * tiles), tile = blockIdx.x - b * (tiles * tiles);
+  const int ty0 = (tile / tiles) * IMG_TILE, tx0 = (tile % tiles) * IMG_TILE;
+  const int h = hw[2 * b], w = hw[2 * b + 1];
+  if (h < 1 || w < 1 || h > IMG_MAX_SIDE || w > IMG_MAX_SIDE) return;   // uniform over the block, before any barrier
+  // geometry: shorter side -> R, the longer one floor(R * long / short); crop origin rounded half to even
+  const int new_long = (int)((long long)R * (w > h ? w : h) / (w > h ? h : w));
+  const int nw = w <= h ? R : new_long, nh = w <= h ? new_long : R;
+  const int qy = (nh - R) >> 1, qx = (nw - R) >> 1;
+  const int top = ((nh - R) & 1) ? qy + (qy & 1) : qy, left = ((nw - R) & 1) ? qx + (qx & 1) : qx;
+  if (t < 2 * IMG_TILE) {
+    const int a = t >> 4, j = t & (IMG_TILE - 1);   // a = 0: columns, 1: rows; indices past R repeat the last one
+    const int i = a ? min(ty0 + j, R - 1) + top : min(tx0 + j, R - 1) + left;
+    axis_setup(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
+  }
+  __syncthreads();
+  const unsigned char* img = src + off[b];
+  const int x = t & (IMG_TILE - 1), y = t >> 4;
+  const int xlo = s_lo[0][x], xhi = s_hi[0][x], xnum = s_num[0][x];
+  const int ylo = s_lo[1][y], yhi = s_hi[1][y], ynum = s_num[1][y];
+  const double xinv = s_inv[0][x];
+  const int M2x = 2 * (w > nw ? w : nw), M2y = 2 * (h > nh ? h : nh);
+  const int vlo = s_lo[1][0], vhi = s_hi[1][IMG_TILE - 1];   // lo and hi do not decrease with the row
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+  for (int v0 = vlo; v0 < vhi; v0 += IMG_TILE) {
+    const int v = v0 + y;   // horizontal pass: this thread's source row of the chunk, output column x
+    if (v < vhi) {
+      const unsigned char* p = img + ((long)v * w + xlo) * 3;
+      double h0 = 0.0, h1 = 0.0, h2 = 0.0;
+      int num = xnum;
+      for (int u = xlo; u < xhi; ++u, p += 3, num += 2 * nw) {
+        const int W = M2x - abs(num);
+        const double dw = (double)(W > 0 ? W : 0);
+        h0 = fma(dw, (double)p[0], h0);
+        h1 = fma(dw, (double)p[1], h1);
+        h2 = fma(dw, (double)p[2], h2);
+      }
+      s_row[y][x][0] = (float)(h0 * xinv);
+      s_row[y][x][1] = (float)(h1 * xinv);
+      s_row[y][x][2] = (float)(h2 * xinv);
+    }
+    __syncthreads();
+    const int r0 = max(ylo - v0, 0), r1 = min(yhi - v0, IMG_TILE);   // vertical pass over the rows of this chunk in [ylo, yhi)
+    int num = ynum + (v0 + r0 - ylo) * (2 * nh);
+    for (int r = r0; r < r1; ++r, num += 2 * nh) {
+      const int W = M2y - abs(num);
+      const double dw = (double)(W > 0 ? W : 0);
+      acc0 = fma(dw, (double)s_row[r][x][0], acc0);
+      acc1 = fma(dw, (double)s_row[r][x][1], acc1);
+      acc2 = fma(dw, (double)s_row[r][x][2], acc2);
+    }
+    __syncthreads();
+  }
+  const int Y = ty0 + y, X = tx0 + x;
+  if (Y >= R || X >= R) return;
+  const double k = s_inv[1][y] * (1.0 / 127.5);   // ToTensor (/255) and Normalize(0.5, 0.5): v / 127.5 - 1
+  const float o0 = (float)(acc0 * k - 1.0), o1 = (float)(acc1 * k - 1.0), o2 = (float)(acc2 * k - 1.0);
+  if (kind == 0) {
+    bf16x8 o = zero8();
+    o[0] = f2bf(o0);
+    o[1] = f2bf(o1);
+    o[2] = f2bf(o2);
+    st8(static_cast<bf16*>(out) + (((long)b * R + Y) * R + X) * 8, o);
+  } else {
+    float* of = static_cast<float*>(out) + ((long)b * 3 * R + Y) * R + X;
+    of[0] = o0;
+    of[(long)R * R] = o1;
+    of[2L * R * R] = o2;
+  }
+}
+
+}  // namespace
+
+extern "C" int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out,
+                               int out_kind, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B < 1 || R < 1 || R > 4096 || (out_kind != 0 && out_kind != 1) || !src || !off || !hw || !out)
+    return DA_ERR_SHAPE;
+  if (out_kind == 0 && ((uintptr_t)out & 15)) return DA_ERR_SHAPE;
+  if (out_kind == 1 && ((uintptr_t)out & 3)) return DA_ERR_SHAPE;
+  const int tiles = (R + IMG_TILE - 1) / IMG_TILE;
+  const long blocks = (long)B * tiles * tiles;
+  if (blocks > 0x7fffffffL) return DA_ERR_SHAPE;
+  hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, R, tiles,
+                     out, out_kind);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}

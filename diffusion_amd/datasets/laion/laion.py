@@ -10,7 +10,9 @@ here, so two backends exist:
     optional ``captions``;
   * no ``remote``/``local`` (the YAML default: both empty) -> a seeded synthetic dataset of the same shapes
     (N(0,1) latents / text embeddings), which is what bench.py and the tests use.
-JPEG decode (:83) is skipped when latents are present: the reference decodes images it never uses."""
+JPEG decode (:83) is skipped when latents are present: the reference decodes images it never uses.  A
+``local`` MDS directory with a ``jpg`` column and no ``latents_{resize_size}`` column is read as raw images instead
+(``datasets/image_ingest.py``): batches then carry ``image_raw`` / ``image_off`` / ``image_hw`` / ``image_size``."""
 from __future__ import annotations
 
 import glob
@@ -152,8 +154,21 @@ def build_streaming_laion_dataloader(
             raise FileNotFoundError(f'local dataset director{"ies" if len(missing) > 1 else "y"} not found: {missing}')
         from ...models.text import build_tokenizer
         tok = build_tokenizer(tokenizer_name_or_path if os.path.isdir(str(tokenizer_name_or_path)) else None)
-        parts = [MDSLatentDataset(d, resize_size, tok, caption_drop_prob) if os.path.exists(os.path.join(d, 'index.json'))
-                 else LocalLatentShards(d, resize_size) for d in local]
+        # an MDS directory of raw images (a `jpg` column and no latents for this resolution - the reference's own LAION
+        # shards, laion.py:81-100): the workers decode, the packed uint8 pixels go to the device and the HIP ingest kernel
+        # does the reference's transform there (datasets/image_ingest.py)
+        from ..image_ingest import MDSImageDataset, collate_raw_images, is_raw_image_directory
+        raw = [os.path.exists(os.path.join(d, 'index.json')) and is_raw_image_directory(d, resize_size) for d in local]
+        if any(raw) and not all(raw):
+            raise ValueError('raw-image and latent directories cannot be mixed in one dataloader: '
+                             f'{[d for d, r in zip(local, raw) if r]} hold images only')
+        if all(raw):
+            parts = [MDSImageDataset(d, tok, caption_drop_prob) for d in local]
+            dataloader_kwargs.setdefault('collate_fn', collate_raw_images(
+                resize_size, pin_memory=bool(dataloader_kwargs.get('pin_memory')) and not dataloader_kwargs.get('num_workers')))
+        else:
+            parts = [MDSLatentDataset(d, resize_size, tok, caption_drop_prob) if os.path.exists(os.path.join(d, 'index.json'))
+                     else LocalLatentShards(d, resize_size) for d in local]
         dataset = torch.utils.data.ConcatDataset(parts)
     else:  # both remote and local empty (the shipped YAML): seeded synthetic data of the same shapes
         dataset = SyntheticLAIONDataset(image_size=resize_size, caption_drop_prob=caption_drop_prob, text_dim=text_dim,

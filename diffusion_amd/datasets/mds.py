@@ -1,5 +1,5 @@
-"""Reader (and a minimal writer, for tests) of MosaicML-streaming "MDS" shards - the on-disk format the reference's
-precomputed latents live in (written by /root/reference scripts/precompute_latents.py:252-328 through
+"""Reader (and a minimal writer, for tests and tools/precompute_latents.py) of MosaicML-streaming "MDS" shards - the
+on-disk format the reference's precomputed latents live in (written by /root/reference scripts/precompute_latents.py:252-328 through
 ``streaming.MDSWriter``; read by diffusion/datasets/laion/laion.py:81-112 through ``streaming.StreamingDataset``).
 
 ``mosaicml-streaming`` is not installed here, so the format is restated from its published layout (format "mds",
@@ -109,31 +109,65 @@ class MDSDirectory:
         return self.shards[si].get(idx - int(self._cum[si]), columns)
 
 
+class MDSWriter:
+    """Incremental writer of the same layout (local conversion of latents, tests): columns sorted by name and the config
+    blob in front of the samples, as ``streaming.MDSWriter`` lays a shard out; no compression, no hashes.  A shard is
+    closed after ``samples_per_shard`` samples or once its sample blobs reach ``size_limit`` bytes (the uint32 offsets
+    bound a shard at 4 GiB); only the open shard is held in memory.  ``finish()`` writes ``index.json``."""
+
+    def __init__(self, directory: str, columns: Dict[str, str], samples_per_shard: int = 1 << 30,
+                 size_limit: Optional[int] = None):
+        os.makedirs(directory, exist_ok=True)
+        self.directory = directory
+        self.names = sorted(columns)
+        self.encs = [columns[n] for n in self.names]
+        self.sizes = [_fixed_size(e) for e in self.encs]
+        self.config = json.dumps({'column_encodings': self.encs, 'column_names': self.names, 'column_sizes': self.sizes,
+                                  'compression': None, 'format': 'mds', 'hashes': [], 'size_limit': None, 'version': 2},
+                                 sort_keys=True).encode('utf-8')
+        self.samples_per_shard, self.size_limit = int(samples_per_shard), size_limit
+        self.shards: List[dict] = []
+        self._blobs: List[bytes] = []
+        self._bytes = 0
+
+    def write(self, smp: dict):
+        payload = [_encode(e, smp[n]) for n, e in zip(self.names, self.encs)]
+        head = b''.join(np.uint32(len(p)).tobytes() for p, s in zip(payload, self.sizes) if s is None)
+        blob = head + b''.join(payload)
+        if self._blobs and self.size_limit and self._bytes + len(blob) > self.size_limit:
+            self._flush()
+        self._blobs.append(blob)
+        self._bytes += len(blob)
+        if len(self._blobs) >= self.samples_per_shard:
+            self._flush()
+
+    def _flush(self):
+        blobs, self._blobs, self._bytes = self._blobs, [], 0
+        if not blobs:
+            return
+        n = len(blobs)
+        header = 4 + 4 * (n + 1) + len(self.config)
+        offs = np.cumsum([header] + [len(b) for b in blobs])
+        if int(offs[-1]) >= 1 << 32:
+            raise ValueError('MDS shard larger than 4 GiB: lower samples_per_shard / size_limit')
+        offs = offs.astype(np.uint32)
+        base = f'shard.{len(self.shards):05d}.mds'
+        with open(os.path.join(self.directory, base), 'wb') as f:
+            f.write(np.uint32(n).tobytes() + offs.tobytes() + self.config + b''.join(blobs))
+        self.shards.append({'column_encodings': self.encs, 'column_names': self.names, 'column_sizes': self.sizes,
+                            'compression': None, 'format': 'mds', 'hashes': [],
+                            'raw_data': {'basename': base, 'bytes': int(offs[-1]), 'hashes': {}}, 'samples': n,
+                            'size_limit': None, 'version': 2, 'zip_data': None})
+
+    def finish(self):
+        self._flush()
+        with open(os.path.join(self.directory, 'index.json'), 'w') as f:
+            json.dump({'shards': self.shards, 'version': 2}, f)
+
+
 def write_mds(directory: str, columns: Dict[str, str], samples: List[dict], samples_per_shard: int = 1 << 30):
-    """Minimal writer of the same layout (tests / local conversion of latents): columns sorted by name and the config
-    blob in front of the samples, as ``streaming.MDSWriter`` lays a shard out; no compression, no hashes."""
-    os.makedirs(directory, exist_ok=True)
-    names = sorted(columns)
-    encs = [columns[n] for n in names]
-    sizes = [_fixed_size(e) for e in encs]
-    config = json.dumps({'column_encodings': encs, 'column_names': names, 'column_sizes': sizes, 'compression': None,
-                         'format': 'mds', 'hashes': [], 'size_limit': None, 'version': 2}, sort_keys=True).encode('utf-8')
-    shards = []
-    for si, start in enumerate(range(0, len(samples), samples_per_shard)):
-        chunk = samples[start:start + samples_per_shard]
-        blobs = []
-        for smp in chunk:
-            payload = [_encode(e, smp[n]) for n, e in zip(names, encs)]
-            head = b''.join(np.uint32(len(p)).tobytes() for p, s in zip(payload, sizes) if s is None)
-            blobs.append(head + b''.join(payload))
-        n = len(chunk)
-        header = 4 + 4 * (n + 1) + len(config)
-        offs = np.cumsum([header] + [len(b) for b in blobs]).astype(np.uint32)
-        base = f'shard.{si:05d}.mds'
-        with open(os.path.join(directory, base), 'wb') as f:
-            f.write(np.uint32(n).tobytes() + offs.tobytes() + config + b''.join(blobs))
-        shards.append({'column_encodings': encs, 'column_names': names, 'column_sizes': sizes, 'compression': None,
-                       'format': 'mds', 'hashes': [], 'raw_data': {'basename': base, 'bytes': int(offs[-1]), 'hashes': {}},
-                       'samples': n, 'size_limit': None, 'version': 2, 'zip_data': None})
-    with open(os.path.join(directory, 'index.json'), 'w') as f:
-        json.dump({'shards': shards, 'version': 2}, f)
+    """All ``samples`` at once through ``MDSWriter``."""
+    w = MDSWriter(directory, columns, samples_per_shard)
+    for smp in samples:
+        w.write(smp)
+    w.finish()

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from .. import ops
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
 from .unet import UNetHIP
+from .vae import DiagonalGaussian
 
 try:
     from tqdm.auto import tqdm
@@ -135,19 +136,43 @@ class StableDiffusion(ComposerModel):
         enc = getattr(self, 'text_hip', None)
         return (enc if enc is not None else self.text_encoder)(input_ids)[0]
 
+    def ingest_raw(self, batch):
+        """A batch of packed raw images (``image_raw`` / ``image_off`` / ``image_hw`` from
+        ``datasets.image_ingest.collate_raw_images``) -> the same batch with the three keys replaced by what the image encoder
+        reads: ``image_nhwc8`` bf16 [B, R, R, 8] for the HIP VAE encoder, else the reference's fp32 ``image`` [B, 3, R, R].
+        One non-blocking upload of the bytes and one kernel (``ops.image_ingest``): the reference's LargestCenterSquare ->
+        ToTensor -> Normalize (laion.py:159-164).  R is the batch's ``image_size`` (the side the dataloader was built
+        with), else ``unet.config.sample_size * 8``."""
+        from ..datasets.image_ingest import RAW_KEYS, ingest_batch
+        R = int(batch.get('image_size') or self.unet.config.sample_size * 8)
+        hip = getattr(self, 'vae_hip', None) is not None
+        out = ingest_batch(batch, R, 0 if hip else 1, self.unet.device_)
+        rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k != 'image_size'}
+        rest['image_nhwc8' if hip else self.image_key] = out.view(-1, R, R, 8) if hip else out
+        return rest
+
     def _encode(self, batch):
         """latents / conditioning selection, reference :155-174."""
         if self.precomputed_latents and self.image_latents_key in batch and self.text_latents_key in batch:
             return batch[self.image_latents_key], batch[self.text_latents_key]
         if self.vae is None or self.text_encoder is None:
             raise RuntimeError('this model was built without VAE / text encoder; pass precomputed latents')
-        inputs, conditioning = batch[self.image_key], batch[self.text_key]
+        if 'image_raw' in batch:
+            batch = self.ingest_raw(batch)
+        vae_hip = getattr(self, 'vae_hip', None)
+        nhwc8 = batch.get('image_nhwc8') if vae_hip is not None else None
+        inputs, conditioning = (None if nhwc8 is not None else batch[self.image_key]), batch[self.text_key]
         conditioning = conditioning.view(-1, conditioning.shape[-1])
         # image encoder: the HIP-kernel walk of the same frozen weights when the factory built one (models/vae_hip.py),
         # else the PyTorch-ROCm module
-        vae_hip = getattr(self, 'vae_hip', None)
         with torch.no_grad():
-            if vae_hip is not None:
+            if nhwc8 is not None:   # ingested raw images, already in conv_in's layout
+                Bn, Hn, Wn, _ = nhwc8.shape
+                mom = vae_hip.moments_nhwc8(nhwc8.contiguous().view(-1, 8), Bn, Hn, Wn)
+                latents = DiagonalGaussian(mom).sample().data
+                with torch.autocast('cuda', enabled=False):
+                    conditioning = self._text_states(conditioning)
+            elif vae_hip is not None:
                 latents = vae_hip.encode(inputs)['latent_dist'].sample().data
                 with torch.autocast('cuda', enabled=False):
                     conditioning = self._text_states(conditioning)

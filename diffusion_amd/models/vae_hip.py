@@ -178,6 +178,15 @@ class VAEEncoderHIP(_VAEWalkHIP):
             raise ValueError('VAEEncoderHIP: images must be [B,3,H,W] with H, W multiples of 8')
         x = torch.zeros(B * H * W, 8, device=self.dev, dtype=BF16)   # NHWC, 3 channels padded to 8
         x.view(B, H, W, 8)[..., :3] = images.to(self.dev).permute(0, 2, 3, 1)
+        return self.moments_nhwc8(x, B, H, W)
+
+    @torch.no_grad()
+    def moments_nhwc8(self, x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """``moments`` of images already in the layout conv_in reads: bf16 [B*H*W, 8] NHWC, channels 3..7 zero (what
+        ``ops.image_ingest`` kind 0 writes)."""
+        if H % 8 or W % 8 or x.dtype != BF16 or not x.is_cuda or not x.is_contiguous() or x.numel() != B * H * W * 8:
+            raise ValueError('VAEEncoderHIP: x must be a contiguous bf16 [B*H*W, 8] device tensor, H and W multiples of 8')
+        x = x.view(B * H * W, 8)
         h = self._bf(B * H * W, self.w['conv_in'].shape[0])
         ops.gemm_nt(x, self.w['conv_in'], h, Geom.conv(B, H, W), bias=self.v['conv_in.bias'])
         del x

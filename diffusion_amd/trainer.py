@@ -212,6 +212,8 @@ class Trainer:
             else:
                 lat = batch.get(model.image_latents_key) if model.precomputed_latents else batch.get(model.image_key)
                 side = 32 if lat is None else (lat.shape[-1] if model.precomputed_latents else lat.shape[-1] // 8)
+                if lat is None and not model.precomputed_latents and 'image_nhwc8' in batch:   # ingested raw images [B,R,R,8]
+                    side = batch['image_nhwc8'].shape[1] // 8
             mb = self.auto_microbatch(n, side)
         starts = list(range(0, n, mb))
         # the first backward of the step WRITES the flat gradient (no zero fill, no read half of the read-add-writes); a
@@ -297,6 +299,8 @@ class Trainer:
                 it = iter(self.dataloader)
                 batch = next(it)
             dev = self.model.unet.device_
+            if 'image_raw' in batch:   # packed raw images: upload + the ingest kernel, while the offset tables are still on the host
+                batch = self.model.ingest_raw(batch)
             batch = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
             loss = self.train_batch(batch)
             self.batch_idx += 1
@@ -330,6 +334,8 @@ class Trainer:
         for i, batch in enumerate(self.eval_dataloader):
             if n is not None and n >= 0 and i >= n:
                 break
+            if 'image_raw' in batch:
+                batch = model.ingest_raw(batch)
             batch = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
             outputs = model.eval_forward(batch)
             for m in metrics.values():

@@ -260,6 +260,19 @@ int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f
                     const float* sqrt_1mac, void* xt, float* target, int B, int C, int HW, int target_kind,
                     da_stream_t stream);
 
+/* LargestCenterSquare(R) + ToTensor + Normalize(0.5,0.5) of B packed RGB uint8 images (transforms.py:9-21, laion.py:159-164):
+ * PIL's antialiased bilinear resize of the shorter side to R (the longer one to floor(R*long/short)), the centre crop with
+ * its origin rounded half to even, then v / 127.5 - 1.  src: tightly packed HWC images (row stride 3*w); off[b]: byte offset
+ * of image b, any alignment; hw[b] = {h, w}, 1 <= h, w <= 65535 (an image outside that range is skipped: nothing is written
+ * for it); the caller guarantees off[b] + 3*h*w <= size of src - every read lies inside that range of its own image.
+ * out_kind 0: bf16 [B*R*R][8] NHWC, channels 3..7 exact zeros, 16-byte aligned (what the VAE encoder's conv_in reads);
+ * out_kind 1: fp32 [B][3][R][R].  Kind 0 is the round-to-nearest-even bf16 of kind 1's value.  Filter weights are exact
+ * integers and the sums run in fp64 (a constant image stays exactly constant); unlike PIL nothing is rounded to uint8
+ * between the passes, so the result is within one uint8 step (2/255) of the reference pipeline.  No workspace.
+ * DA_ERR_SHAPE for B < 1, R outside 1..4096, an unknown out_kind or a misaligned out. */
+int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out, int out_kind,
+                    da_stream_t stream);
+
 /* F.mse_loss(pred, target) (stable_diffusion.py:187) over the 4 valid channels of NHWC(8) fp32 tensors and its
  * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats */
 int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
