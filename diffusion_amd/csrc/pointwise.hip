@@ -2,7 +2,9 @@
 // GEGLU, SiLU, strided add / copy (skip-connection concat), nearest-2x upsample fwd/bwd, sinusoidal
 // timestep embedding, forward-diffusion noising (NCHW fp32 -> NHWC-8 bf16), fused MSE loss + gradient,
 // fused AdamW (fp32 master + moments, bf16 shadow write), weight-shadow transpose for dgrad.
-// All use 16-B vector accesses along the contiguous (channel) axis and grid-stride loops.
+// All use 16-B vector accesses along the contiguous (channel) axis and grid-stride loops.  GEGLU, SiLU, the two GELUs, add and
+// copy are instances of one kernel, map2d_kernel<Op, NIN, NOUT>, behind one launcher; the 4-channel latent loss runs the
+// general mse_partial_c_kernel at C = 4.
 #include "common.hpp"
 #include "diffusion_amd.h"
 
@@ -18,106 +20,89 @@ inline int pw_blocks(long n) {
 #define GRID_STRIDE(i, n) \
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
-// ---- GEGLU: out = a * gelu(g), in = [a | g]
-__global__ void geglu_fwd_kernel(const bf16* in, long ldi, bf16* out, long ldo, int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(in + row * ldi + 8 * v);
-    bf16x8 g = ld8(in + row * ldi + 8 * (nvec + v));
-    bf16x8 o;
+// ---- the strided map: the eight pointwise entry points whose work item is 16 bytes of every operand at [row, 8 v], each
+// operand at its own row stride.  All NIN loads come before the first store, so an output may be one of the inputs.
+template <int NIN, int NOUT>
+struct Map2dArgs {
+  const bf16* in[NIN];
+  long ldi[NIN];
+  bf16* out[NOUT];
+  long ldo[NOUT];
+  int nvec;
+  long total;
+};
+template <typename Op, int NIN, int NOUT>
+__global__ void map2d_kernel(Map2dArgs<NIN, NOUT> p) {
+  GRID_STRIDE(i, p.total) {
+    long row = i / p.nvec;
+    int v = (int)(i - row * p.nvec);
+    bf16x8 x[NIN], y[NOUT];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(a[e]) * gelu_f(bf2f(g[e])));
-    st8(out + row * ldo + 8 * v, o);
-  }
-}
-__global__ void geglu_bwd_kernel(const bf16* in, long ldi, const bf16* dout, long lddo, bf16* din, long lddi,
-                                 int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(in + row * ldi + 8 * v);
-    bf16x8 g = ld8(in + row * ldi + 8 * (nvec + v));
-    bf16x8 d = ld8(dout + row * lddo + 8 * v);
-    bf16x8 da, dg;
+    for (int k = 0; k < NIN; ++k) x[k] = ld8(p.in[k] + row * p.ldi[k] + 8 * v);
+    Op::apply(x, y);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float gf = bf2f(g[e]), df = bf2f(d[e]);
-      da[e] = f2bf(df * gelu_f(gf));
-      dg[e] = f2bf(df * bf2f(a[e]) * dgelu_f(gf));
-    }
-    st8(din + row * lddi + 8 * v, da);
-    st8(din + row * lddi + 8 * (nvec + v), dg);
+    for (int k = 0; k < NOUT; ++k) st8(p.out[k] + row * p.ldo[k] + 8 * v, y[k]);
   }
 }
 
+// Op::apply(x, y): whole 16-byte vectors in and out, so a copy never passes through fp32
+// ---- GEGLU: out = a * gelu(g), in = [a | g]: the gate half is a second operand at in + Cout with the same stride
+struct GegluFwd {  // x = {a, g}
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) y[0][e] = f2bf(bf2f(x[0][e]) * gelu_f(bf2f(x[1][e])));
+  }
+};
+struct GegluBwd {  // x = {a, g, dout}, y = {da, dg}
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float gf = bf2f(x[1][e]), df = bf2f(x[2][e]);
+      y[0][e] = f2bf(df * gelu_f(gf));
+      y[1][e] = f2bf(df * bf2f(x[0][e]) * dgelu_f(gf));
+    }
+  }
+};
 // ---- SiLU on a 2-D strided tensor
-__global__ void silu_fwd_kernel(const bf16* x, long ldx, bf16* y, long ldy, int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(x + row * ldx + 8 * v), o;
+struct SiluFwd {
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(silu_f(bf2f(a[e])));
-    st8(y + row * ldy + 8 * v, o);
+    for (int e = 0; e < 8; ++e) y[0][e] = f2bf(silu_f(bf2f(x[0][e])));
   }
-}
+};
+struct SiluBwd {  // x = {x, dy}
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) y[0][e] = f2bf(bf2f(x[1][e]) * dsilu_f(bf2f(x[0][e])));
+  }
+};
 // ---- erf-GELU on a 2-D strided tensor (the text encoder's MLP activation; forward only - the encoder is frozen)
-__global__ void gelu_fwd_kernel(const bf16* x, long ldx, bf16* y, long ldy, int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(x + row * ldx + 8 * v), o;
+struct GeluFwd {
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_f(bf2f(a[e])));
-    st8(y + row * ldy + 8 * v, o);
+    for (int e = 0; e < 8; ++e) y[0][e] = f2bf(gelu_f(bf2f(x[0][e])));
   }
-}
+};
 // ---- quick-GELU x * sigmoid(1.702 x) (CLIP ViT-L/14's MLP activation, hidden_act = "quick_gelu"); forward only
-__global__ void quick_gelu_fwd_kernel(const bf16* x, long ldx, bf16* y, long ldy, int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(x + row * ldx + 8 * v), o;
+struct QuickGeluFwd {
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float f = bf2f(a[e]);
-      o[e] = f2bf(f / (1.0f + expf(-1.702f * f)));
+      const float f = bf2f(x[0][e]);
+      y[0][e] = f2bf(f / (1.0f + expf(-1.702f * f)));
     }
-    st8(y + row * ldy + 8 * v, o);
   }
-}
-__global__ void silu_bwd_kernel(const bf16* x, long ldx, const bf16* dy, long lddy, bf16* dx, long lddx, int nvec,
-                                long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 a = ld8(x + row * ldx + 8 * v), d = ld8(dy + row * lddy + 8 * v), o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(d[e]) * dsilu_f(bf2f(a[e])));
-    st8(dx + row * lddx + 8 * v, o);
-  }
-}
-
+};
 // ---- strided add / copy
-__global__ void add_kernel(const bf16* a, long lda, const bf16* b, long ldb, bf16* o, long ldo, int nvec,
-                           long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    bf16x8 x = ld8(a + row * lda + 8 * v), y = ld8(b + row * ldb + 8 * v), r;
+struct Add {
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = f2bf(bf2f(x[e]) + bf2f(y[e]));
-    st8(o + row * ldo + 8 * v, r);
+    for (int e = 0; e < 8; ++e) y[0][e] = f2bf(bf2f(x[0][e]) + bf2f(x[1][e]));
   }
-}
-__global__ void copy2d_kernel(const bf16* a, long lda, bf16* o, long ldo, int nvec, long total) {
-  GRID_STRIDE(i, total) {
-    long row = i / nvec;
-    int v = (int)(i - row * nvec);
-    st8(o + row * ldo + 8 * v, ld8(a + row * lda + 8 * v));
-  }
-}
+};
+struct Copy2d {
+  static DEVINL void apply(const bf16x8* x, bf16x8* y) { y[0] = x[0]; }
+};
 
 // ---- nearest 2x upsample (NHWC)
 __global__ void upsample2x_fwd_kernel(const bf16* x, bf16* y, int H, int W, int nvec, long total_out) {
@@ -174,7 +159,10 @@ __global__ void timestep_embed_kernel(const T* t, bf16* out, int B, int dim) {
 }
 
 // ---- forward diffusion: x_t = sqrt(ac[t]) x0 + sqrt(1-ac[t]) eps ; target = eps or v
-// inputs NCHW fp32 [B,4,HW]; outputs NHWC with the 4 channels padded to 8 (pad = 0)
+// inputs NCHW fp32 [B,4,HW]; outputs NHWC with the 4 channels padded to 8 (pad = 0).  Not the C = 4 case of the general
+// kernel below: here the compiler fuses a x + (s n) into an FMA, there it adds two rounded products, and among millions of
+// pixels a few bf16 x_t differ by that (the v target is unfused in both); without the run-time channel count a launch at
+// the U-Net's sizes also takes 5.2 us against 6.0 us (MI355X)
 __global__ void add_noise_kernel(const float* x0, const float* eps, const long long* t, const float* sqrt_ac,
                                  const float* sqrt_1mac, bf16* xt, float* target, int HW, long total_pix,
                                  int v_pred) {
@@ -231,41 +219,32 @@ __global__ void add_noise_ex_kernel(const float* x0, const float* eps, const voi
   }
 }
 
-// ---- MSE loss over the 4 valid channels of NHWC-8 tensors, and its gradient
-__global__ void mse_partial_kernel(const float* pred, const float* target, bf16* dpred, float* partial,
-                                   long total_pix, float grad_coef) {
+// ---- sum over the block: wave butterfly, one partial per wave in LDS, thread 0 adds them in wave order (valid in thread 0)
+DEVINL float block_sum(float acc) {
   __shared__ float sh[PW_BLOCK / 64];
-  float acc = 0.f;
-  GRID_STRIDE(i, total_pix) {
-    f32x4 p = *reinterpret_cast<const f32x4*>(pred + i * 8);
-    f32x4 q = *reinterpret_cast<const f32x4*>(target + i * 8);
-    bf16x8 g = zero8();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float d = p[c] - q[c];
-      acc += d * d;
-      g[c] = f2bf(d * grad_coef);
-    }
-    st8(dpred + i * 8, g);
-  }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
+  float s = 0.f;
+  if (threadIdx.x == 0)
     for (int w = 0; w < PW_BLOCK / 64; ++w) s += sh[w];
-    partial[blockIdx.x] = s;
-  }
+  return s;
 }
-// ---- the same over C (1..8) valid channels; dpred is exactly 0 in the pad channels
+
+// ---- MSE loss over the C (1..8) valid channels of NHWC-8 tensors, and its gradient; dpred is exactly 0 in the pad channels
 __global__ void mse_partial_c_kernel(const float* pred, const float* target, bf16* dpred, float* partial,
                                      long total_pix, int C, float grad_coef) {
-  __shared__ float sh[PW_BLOCK / 64];
   float acc = 0.f;
   GRID_STRIDE(i, total_pix) {
-    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
-    const f32x4 q0 = *reinterpret_cast<const f32x4*>(target + i * 8),
-                q1 = *reinterpret_cast<const f32x4*>(target + i * 8 + 4);
+    // each square is rounded to fp32 and then added, never fused into an FMA: these are the bits the 4-channel latent loss
+    // has always had (its former kernel of its own compiled to packed multiplies), whatever the compiler would choose here
+#pragma clang fp contract(off)
+    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), q0 = *reinterpret_cast<const f32x4*>(target + i * 8);
+    f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 0.f, 0.f};
+    if (C > 4) {  // uniform: the 4-channel (latent) loss reads the lower 16 bytes of a pixel only
+      p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
+      q1 = *reinterpret_cast<const f32x4*>(target + i * 8 + 4);
+    }
     bf16x8 g = zero8();
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -277,26 +256,15 @@ __global__ void mse_partial_c_kernel(const float* pred, const float* target, bf1
     }
     st8(dpred + i * 8, g);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int w = 0; w < PW_BLOCK / 64; ++w) s += sh[w];
-    partial[blockIdx.x] = s;
-  }
+  const float s = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 __global__ void mse_finalize_kernel(const float* partial, int n, float* loss, float inv_count, float weight,
                                     int accumulate) {
-  __shared__ float sh[PW_BLOCK / 64];
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partial[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  float s = block_sum(acc);
   if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int w = 0; w < PW_BLOCK / 64; ++w) s += sh[w];
     s = s * inv_count * weight;
     loss[0] = accumulate ? loss[0] + s : s;
   }
@@ -433,95 +401,61 @@ __global__ __launch_bounds__(256) void transpose_weights_batched_kernel(const bf
 
 }  // namespace
 
-#define CHK8(x) if ((x) & 7) return DA_ERR_SHAPE
-
-extern "C" int da_geglu_fwd(const void* in, long ldi, void* out, long ldo, int M, int Cout, hipStream_t s) {
+// The eight map entry points: C and every row stride a multiple of 8 elements, then one launch
+template <typename Op, int NIN, int NOUT>
+int map2d_launch(const void* const (&in)[NIN], const long (&ldi)[NIN], void* const (&out)[NOUT],
+                 const long (&ldo)[NOUT], int M, int C, hipStream_t s) {
   DA_CLEAR_ERR();
-  if (M <= 0 || Cout <= 0) return DA_ERR_SHAPE;
-  CHK8(Cout); CHK8(ldi); CHK8(ldo);
-  long total = (long)M * (Cout >> 3);
-  hipLaunchKernelGGL(geglu_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)in, ldi,
-                     (bf16*)out, ldo, Cout >> 3, total);
+  if (M <= 0 || C <= 0 || (C & 7)) return DA_ERR_SHAPE;
+  Map2dArgs<NIN, NOUT> p;
+  for (int k = 0; k < NIN; ++k) {
+    if (ldi[k] & 7) return DA_ERR_SHAPE;
+    p.in[k] = (const bf16*)in[k];
+    p.ldi[k] = ldi[k];
+  }
+  for (int k = 0; k < NOUT; ++k) {
+    if (ldo[k] & 7) return DA_ERR_SHAPE;
+    p.out[k] = (bf16*)out[k];
+    p.ldo[k] = ldo[k];
+  }
+  p.nvec = C >> 3;
+  p.total = (long)M * p.nvec;
+  hipLaunchKernelGGL((map2d_kernel<Op, NIN, NOUT>), dim3(pw_blocks(p.total)), dim3(PW_BLOCK), 0, s, p);
   DA_CHECK_LAUNCH();
   return DA_OK;
+}
+
+extern "C" int da_geglu_fwd(const void* in, long ldi, void* out, long ldo, int M, int Cout, hipStream_t s) {
+  return map2d_launch<GegluFwd, 2, 1>({in, (const bf16*)in + Cout}, {ldi, ldi}, {out}, {ldo}, M, Cout, s);
 }
 extern "C" int da_geglu_bwd(const void* in, long ldi, const void* dout, long lddo, void* din, long lddi, int M,
                             int Cout, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || Cout <= 0) return DA_ERR_SHAPE;
-  CHK8(Cout); CHK8(ldi); CHK8(lddo); CHK8(lddi);
-  long total = (long)M * (Cout >> 3);
-  hipLaunchKernelGGL(geglu_bwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)in, ldi,
-                     (const bf16*)dout, lddo, (bf16*)din, lddi, Cout >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<GegluBwd, 3, 2>({in, (const bf16*)in + Cout, dout}, {ldi, ldi, lddo}, {din, (bf16*)din + Cout},
+                                      {lddi, lddi}, M, Cout, s);
 }
 extern "C" int da_silu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(ldx); CHK8(ldy);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(silu_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, ldx, (bf16*)y,
-                     ldy, C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<SiluFwd, 1, 1>({x}, {ldx}, {y}, {ldy}, M, C, s);
 }
 extern "C" int da_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(ldx); CHK8(ldy);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, ldx, (bf16*)y,
-                     ldy, C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<GeluFwd, 1, 1>({x}, {ldx}, {y}, {ldy}, M, C, s);
 }
 extern "C" int da_quick_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int C, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(ldx); CHK8(ldy);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(quick_gelu_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, ldx,
-                     (bf16*)y, ldy, C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<QuickGeluFwd, 1, 1>({x}, {ldx}, {y}, {ldy}, M, C, s);
 }
 extern "C" int da_silu_bwd(const void* x, long ldx, const void* dy, long lddy, void* dx, long lddx, int M, int C,
                            hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(ldx); CHK8(lddy); CHK8(lddx);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(silu_bwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, ldx,
-                     (const bf16*)dy, lddy, (bf16*)dx, lddx, C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<SiluBwd, 2, 1>({x, dy}, {ldx, lddy}, {dx}, {lddx}, M, C, s);
 }
 extern "C" int da_add(const void* a, long lda, const void* b, long ldb, void* o, long ldo, int M, int C,
                       hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(lda); CHK8(ldb); CHK8(ldo);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(add_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)a, lda, (const bf16*)b,
-                     ldb, (bf16*)o, ldo, C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<Add, 2, 1>({a, b}, {lda, ldb}, {o}, {ldo}, M, C, s);
 }
 extern "C" int da_copy2d(const void* a, long lda, void* o, long ldo, int M, int C, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (M <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C); CHK8(lda); CHK8(ldo);
-  long total = (long)M * (C >> 3);
-  hipLaunchKernelGGL(copy2d_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)a, lda, (bf16*)o, ldo,
-                     C >> 3, total);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return map2d_launch<Copy2d, 1, 1>({a}, {lda}, {o}, {ldo}, M, C, s);
 }
 extern "C" int da_upsample2x_fwd(const void* x, void* y, int B, int H, int W, int C, hipStream_t s) {
   DA_CLEAR_ERR();
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C);
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7)) return DA_ERR_SHAPE;
   long total = (long)B * 4 * H * W * (C >> 3);
   hipLaunchKernelGGL(upsample2x_fwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)x, (bf16*)y,
                      H, W, C >> 3, total);
@@ -530,8 +464,7 @@ extern "C" int da_upsample2x_fwd(const void* x, void* y, int B, int H, int W, in
 }
 extern "C" int da_upsample2x_bwd(const void* dy, void* dx, int B, int H, int W, int C, hipStream_t s) {
   DA_CLEAR_ERR();
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return DA_ERR_SHAPE;
-  CHK8(C);
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7)) return DA_ERR_SHAPE;
   long total = (long)B * H * W * (C >> 3);
   hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, (const bf16*)dy, (bf16*)dx,
                      H, W, C >> 3, total);
@@ -558,24 +491,11 @@ extern "C" int da_add_noise(const float* x0, const float* eps, const long long* 
                             const float* sqrt_1mac, void* xt, float* target, int B, int HW, int v_pred,
                             hipStream_t s) {
   DA_CLEAR_ERR();
-  if (B <= 0 || HW <= 0) return DA_ERR_SHAPE;
+  if (B <= 0 || HW <= 0 || !t || !sqrt_ac || !sqrt_1mac) return DA_ERR_SHAPE;
+  if (((uintptr_t)xt & 15) || ((uintptr_t)target & 15)) return DA_ERR_SHAPE;
   long total = (long)B * HW;
   hipLaunchKernelGGL(add_noise_kernel, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, x0, eps, t, sqrt_ac, sqrt_1mac,
                      (bf16*)xt, target, HW, total, v_pred);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-extern "C" int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
-                           long total_pix, float grad_coef, float weight, int accumulate, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (total_pix <= 0) return DA_ERR_SHAPE;
-  int blocks = pw_blocks(total_pix);
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(blocks), dim3(PW_BLOCK), 0, s, pred, target, (bf16*)dpred, scratch,
-                     total_pix, grad_coef);
-  DA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss,
-                     1.0f / (4.0f * (float)total_pix), weight, accumulate);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -596,8 +516,9 @@ extern "C" int da_add_noise_ex(const float* x0, const float* eps, const void* t,
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
-extern "C" int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
-                             long total_pix, int C, float grad_coef, float weight, int accumulate, hipStream_t s) {
+// both MSE entry points: each computes the reciprocal of its count its own way (they differ in the last bit for some sizes)
+static int mse_launch(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
+                      int C, float grad_coef, float inv_count, float weight, int accumulate, hipStream_t s) {
   DA_CLEAR_ERR();
   if (total_pix <= 0 || C < 1 || C > 8) return DA_ERR_SHAPE;
   if ((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) & 15)) return DA_ERR_SHAPE;
@@ -606,10 +527,20 @@ extern "C" int da_mse_loss_c(const float* pred, const float* target, void* dpred
   hipLaunchKernelGGL(mse_partial_c_kernel, dim3(blocks), dim3(PW_BLOCK), 0, s, pred, target, (bf16*)dpred, scratch,
                      total_pix, C, grad_coef);
   DA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss,
-                     (float)(1.0 / ((double)C * (double)total_pix)), weight, accumulate);
+  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss, inv_count, weight,
+                     accumulate);
   DA_CHECK_LAUNCH();
   return DA_OK;
+}
+extern "C" int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
+                           long total_pix, float grad_coef, float weight, int accumulate, hipStream_t s) {
+  return mse_launch(pred, target, dpred, loss, scratch, total_pix, 4, grad_coef, 1.0f / (4.0f * (float)total_pix), weight,
+                    accumulate, s);
+}
+extern "C" int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
+                             long total_pix, int C, float grad_coef, float weight, int accumulate, hipStream_t s) {
+  return mse_launch(pred, target, dpred, loss, scratch, total_pix, C, grad_coef,
+                    (float)(1.0 / ((double)C * (double)total_pix)), weight, accumulate, s);
 }
 extern "C" int da_adamw(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing,
                         long n, float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale,

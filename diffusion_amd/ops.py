@@ -415,65 +415,50 @@ def image_colsum(X, out, db, scratch, B, HW):
               _f32buf(scratch, norm_scratch_floats(B, HW, C)), B, HW, C, _stream())
 
 
+def _map2d(entry, *mats, wide=()):
+    """The strided-map entry points: (pointer, row stride) per operand, then M and C.  Every operand is a `_mat` of
+    one shape [M, C]; those at the indices in ``wide`` are GEGLU projections [a | g] of 2 * C columns.  The kernel trusts
+    M and C for every operand, so a smaller one would be read or written past its end.  Returns the last operand."""
+    args = [v for m in mats for v in _mat(m, BF16, entry)]
+    M, C = mats[0].shape[0], mats[0].shape[1] // (2 if 0 in wide else 1)
+    for k, m in enumerate(mats):
+        if tuple(m.shape) != (M, 2 * C if k in wide else C):
+            raise ValueError(f'{entry[3:]}: shape mismatch: operand {k} is {tuple(m.shape)}, operand 0 '
+                             f'{tuple(mats[0].shape)}' + (f' (operands {wide} have twice the columns)' if wide else ''))
+    _lib.call(entry, *args, M, C, _stream())
+    return mats[-1]
+
+
 def geglu_fwd(inp, out):
-    i, ldi = _mat(inp, BF16)
-    o, ldo = _mat(out, BF16)
-    M, C2 = inp.shape
-    _lib.call('da_geglu_fwd', i, ldi, o, ldo, M, C2 // 2, _stream())
+    _map2d('da_geglu_fwd', inp, out, wide=(0,))
 
 
 def geglu_bwd(inp, dout, din):
-    i, ldi = _mat(inp, BF16)
-    d, ldd = _mat(dout, BF16)
-    di, lddi = _mat(din, BF16)
-    M, C2 = inp.shape
-    _lib.call('da_geglu_bwd', i, ldi, d, ldd, di, lddi, M, C2 // 2, _stream())
+    _map2d('da_geglu_bwd', inp, dout, din, wide=(0, 2))
 
 
 def silu_fwd(x, y):
-    a, lda = _mat(x, BF16)
-    b, ldb = _mat(y, BF16)
-    _lib.call('da_silu_fwd', a, lda, b, ldb, x.shape[0], x.shape[1], _stream())
+    _map2d('da_silu_fwd', x, y)
 
 
 def gelu_fwd(x, y):
-    a, lda = _mat(x, BF16)
-    b, ldb = _mat(y, BF16)
-    _lib.call('da_gelu_fwd', a, lda, b, ldb, x.shape[0], x.shape[1], _stream())
+    _map2d('da_gelu_fwd', x, y)
 
 
 def quick_gelu_fwd(x, y):
-    a, lda = _mat(x, BF16)
-    b, ldb = _mat(y, BF16)
-    if x.shape != y.shape:
-        raise ValueError('quick_gelu_fwd: shape mismatch')
-    _lib.call('da_quick_gelu_fwd', a, lda, b, ldb, x.shape[0], x.shape[1], _stream())
+    _map2d('da_quick_gelu_fwd', x, y)
 
 
 def silu_bwd(x, dy, dx):
-    a, lda = _mat(x, BF16)
-    b, ldb = _mat(dy, BF16)
-    c, ldc = _mat(dx, BF16)
-    _lib.call('da_silu_bwd', a, lda, b, ldb, c, ldc, x.shape[0], x.shape[1], _stream())
+    _map2d('da_silu_bwd', x, dy, dx)
 
 
 def add(a, b, out):
-    pa, lda = _mat(a, BF16)
-    pb, ldb = _mat(b, BF16)
-    po, ldo = _mat(out, BF16)
-    if a.shape != b.shape or a.shape != out.shape:
-        raise ValueError('add: shape mismatch')
-    _lib.call('da_add', pa, lda, pb, ldb, po, ldo, a.shape[0], a.shape[1], _stream())
-    return out
+    return _map2d('da_add', a, b, out)
 
 
 def copy2d(a, out):
-    pa, lda = _mat(a, BF16)
-    po, ldo = _mat(out, BF16)
-    if a.shape != out.shape:
-        raise ValueError('copy2d: shape mismatch')
-    _lib.call('da_copy2d', pa, lda, po, ldo, a.shape[0], a.shape[1], _stream())
-    return out
+    return _map2d('da_copy2d', a, out)
 
 
 def upsample2x_bwd(dy, dx, B, H, W, C):

@@ -244,7 +244,9 @@ int da_timestep_embed_f32(const float* t, void* out, int B, int dim, da_stream_t
 
 /* DDPMScheduler.add_noise (stable_diffusion.py:180) fused with the NCHW fp32 -> NHWC(8) bf16 relayout and
  * the training target (eps, or get_velocity when v_pred - pixel_diffusion.py:90-91).
- * x0, eps: [B][4][HW] fp32; xt: [B*HW][8] bf16 (channels 4..7 zero); target: [B*HW][8] fp32. */
+ * x0, eps: [B][4][HW] fp32; xt: [B*HW][8] bf16 (channels 4..7 zero); target: [B*HW][8] fp32.
+ * DA_ERR_SHAPE for a NULL t or table and for an xt or target that is not 16-byte aligned, as da_add_noise_ex (such
+ * arguments were undefined behaviour while this entry did not check them). */
 int da_add_noise(const float* x0, const float* eps, const long long* t, const float* sqrt_ac,
                  const float* sqrt_1mac, void* xt, float* target, int B, int HW, int v_pred, da_stream_t stream);
 
@@ -255,7 +257,9 @@ int da_add_noise(const float* x0, const float* eps, const long long* t, const fl
  *   t_is_f32 = 1: t is fp32 [B] angles, the tangent schedule of schedulers.py:10-24 / :64-79 in the kernel:
  *                 x_t = cos t x0 + sin t eps, v = -sin t x0 + cos t eps; the tables are not read (may be NULL).
  * target_kind: 0 eps, 1 v (v_prediction), 2 x0 (sample).  For C = 4, t_is_f32 = 0 and target_kind 0 / 1 the result is
- * bit-identical to da_add_noise.  DA_ERR_SHAPE for C outside 1..8, an unknown target_kind or missing tables. */
+ * that of da_add_noise up to the rounding of x_t: da_add_noise fuses a x0 + (s eps) into one FMA, so a bf16 x_t in a
+ * million or so differs by one ulp.  DA_ERR_SHAPE for C outside 1..8, an unknown target_kind, a
+ * NULL t, missing tables (t_is_f32 = 0) or a misaligned xt / target. */
 int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f32, const float* sqrt_ac,
                     const float* sqrt_1mac, void* xt, float* target, int B, int C, int HW, int target_kind,
                     da_stream_t stream);
@@ -274,7 +278,8 @@ int da_image_ingest(const unsigned char* src, const long long* off, const int* h
                     da_stream_t stream);
 
 /* F.mse_loss(pred, target) (stable_diffusion.py:187) over the 4 valid channels of NHWC(8) fp32 tensors and its
- * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats */
+ * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats;
+ * pred, target, dpred 16-byte aligned (DA_ERR_SHAPE otherwise). */
 int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
                 float grad_coef, float weight, int accumulate, da_stream_t stream);
 /* the da_mse_loss contract over C = 1..8 valid channels (the 3-channel pixel models' F.mse_loss, pixel_diffusion.py:98):

@@ -2,21 +2,24 @@
 column sums of norms.hip against a float64 reference, at the sizes, values and memory layouts where such kernels go wrong.
 
     kernel(s)                                  | cases                                                  | confirmed by
-    silu_fwd gelu_fwd quick_gelu_fwd           | all 65,280 finite bf16 inputs, [8160, 8] and strided   | sandwich; no NaN; +-0 -> +-0;
+    map2d<SiluFwd / GeluFwd / QuickGeluFwd>    | all 65,280 finite bf16 inputs, [8160, 8] and strided   | sandwich; no NaN; +-0 -> +-0;
                                                | [255, 256], in place too                               | gelu exact beyond |x| > 16
-    silu_bwd                                   | x exhaustive x dy in {1, -1, 2^-20, 3 2^10, randn}     | sandwich
-    geglu_fwd geglu_bwd                        | g exhaustive x a, d in those classes; Cout 8 / 328 /   | sandwich on out, the da half and
+    map2d<SiluBwd>                             | x exhaustive x dy in {1, -1, 2^-20, 3 2^10, randn}     | sandwich
+    map2d<GegluFwd> map2d<GegluBwd>            | g exhaustive x a, d in those classes; Cout 8 / 328 /   | sandwich on out, the da half and
                                                | 1280 x M 1 / 3 / 130                                   | the dg half; a != g distributions
-    add copy2d                                 | random finite bf16 bit patterns, M 1 / 2 / 257,        | exact (the fp32 sum of two bf16 is
+    map2d<Add> map2d<Copy2d>                   | random finite bf16 bit patterns, M 1 / 2 / 257,        | exact (the fp32 sum of two bf16 is
                                                | C 8 / 328, in place (o == a, o == b)                   | exact: one rounding)
+    the eight map2d wrappers of ops.py         | output of another row count, width or GEGLU half       | ValueError, nothing written
     upsample2x_fwd upsample2x_bwd              | (1,1,1,8) (2,1,7,8) (3,5,1,64) (2,5,6,328)             | exact (grid inputs); sandwich N(0,1)
     every grid-stride family                   | > 16384 * 256 work items (mse: > 1024 blocks)          | bit-identical to row slices under
                                                |                                                        | the cap; float64 on a sample
     timestep_embed (int64 and fp32)            | dim 2 / 64 / 320 / 1280, B 1 / 7, t 0 .. 999, angles   | sandwich, [cos | sin] order
     add_noise add_noise_ex<discrete / cont>    | HW 1 / 63 / 65 / 64, B 1 / 4, C 1 .. 8, three targets  | sandwich (xt), fp32 bound (v),
                                                | t = 0 and 999 (angles 0 and 1.570795), |x| 1e-3 .. 1e3 | bit-exact eps / x0, pads +0
-    mse_loss mse_loss_c + mse_finalize         | total_pix 1 / 255 / 257 / 1152, C 1 .. 8, NaN pads     | sandwich (dpred), loss vs float64,
-                                               | integer grid, accumulate 0 / 1, weight 0.25            | exact on the integer grid
+                                               | da_add_noise: misaligned xt / target, NULL table       | DA_ERR_SHAPE, nothing written
+    mse_partial_c + mse_finalize, through      | total_pix 1 / 255 / 257 / 1152, C 1 .. 8, NaN pads     | sandwich (dpred), loss vs float64,
+    da_mse_loss (C = 4) and da_mse_loss_c      | integer grid, accumulate 0 / 1, weight 0.25            | exact on the integer grid; the two
+                                               | misaligned pred / target / dpred                       | entries equal bits; DA_ERR_SHAPE
     cast_f32_bf16                              | every bf16 +- half an ulp (+- 1 fp32 ulp), fp32 max,   | exact: RNE on the bit pattern and
                                                | denormals, +-0, +-inf, NaN; n 1 / 7 / 255 / 257        | torch's fp32 -> bf16
     adamw                                      | n 1 .. 100003, step 1 .. 100000, g = 0, g^2 underflow, | float64 AdamW per element; shadow
@@ -475,6 +478,31 @@ def test_add_copy_exact(dev, ops, M, C):
     assert same_bits(got, a), f'copy2d {M}x{C}'
 
 
+MAP_WRAPPERS = {   # name: (number of inputs, the operands that are GEGLU projections [a | g] of twice the columns)
+    'silu_fwd': (1, ()), 'gelu_fwd': (1, ()), 'quick_gelu_fwd': (1, ()), 'silu_bwd': (2, ()), 'add': (2, ()),
+    'copy2d': (1, ()), 'geglu_fwd': (1, (0,)), 'geglu_bwd': (2, (0, 2)),
+}
+
+
+@pytest.mark.parametrize('name', sorted(MAP_WRAPPERS))
+def test_map_wrappers_reject_mismatched_shapes(dev, ops, name):
+    """[2, 16] inputs (a GEGLU projection: [2, 32]) with an output of 3 rows and with one of half the width; for GEGLU also
+    an out (forward) / dout (backward) as wide as the projection instead of half of it: ValueError, nothing written"""
+    nin, wide = MAP_WRAPPERS[name]
+    shapes = [(2, 32 if k in wide else 16) for k in range(nin + 1)]           # the matching call: inputs, then the output
+    cases = [shapes[:nin] + [(3, shapes[nin][1])], shapes[:nin] + [(2, shapes[nin][1] // 2)]]
+    if wide:
+        narrow = 1                                                             # out of geglu_fwd, dout of geglu_bwd
+        cases.append([(2, 32) if k == narrow else sh for k, sh in enumerate(shapes)])
+    for case in cases:
+        ins = [torch.ones(sh, device=dev, dtype=BF) for sh in case[:nin]]
+        out = torch.full(case[nin], 7.0, device=dev, dtype=BF)
+        with pytest.raises(ValueError):
+            getattr(ops, name)(*ins, out)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), f'{name}: a rejected call on shapes {case} wrote to its output'
+
+
 # ------------------------------------------------------------------------------------------------ upsample
 UPSAMPLE_SHAPES = [(1, 1, 1, 8), (2, 1, 7, 8), (3, 5, 1, 64), (2, 5, 6, 328)]
 
@@ -684,6 +712,23 @@ def test_add_noise_ex(dev, ops, C, cont):
                         f'add_noise_ex C={C} HW={HW} B={B} {kind} {"cont" if cont else "disc"}')
 
 
+def test_add_noise_rejects_misaligned_and_null(dev, ops):
+    """da_add_noise rejects what da_add_noise_ex rejects: B = 1, HW = 1, xt off by 2 bytes, target off by 4 bytes, a NULL
+    table; nothing is written"""
+    sa, s1 = noise_tables(dev)
+    x0, eps = torch.ones(4, device=dev), torch.ones(4, device=dev)
+    t = torch.zeros(1, device=dev, dtype=torch.int64)
+    xt = torch.full((16,), 7.0, device=dev, dtype=BF)
+    tg = torch.full((16,), 5.0, device=dev)
+    from diffusion_amd.ops import _stream
+    for off_x, off_t, table in ((2, 0, sa.data_ptr()), (0, 4, sa.data_ptr()), (0, 0, None)):
+        with pytest.raises(RuntimeError, match='DA_ERR_SHAPE'):
+            ops._lib.call('da_add_noise', x0.data_ptr(), eps.data_ptr(), t.data_ptr(), table, s1.data_ptr(),
+                          xt.data_ptr() + off_x, tg.data_ptr() + off_t, 1, 1, 0, _stream())
+    torch.cuda.synchronize()
+    assert bool((xt == 7.0).all()) and bool((tg == 5.0).all())
+
+
 # ------------------------------------------------------------------------------------------------ MSE loss
 def mse_geometry(total_pix, C):
     """(blocks, additions on the longest path from a term to the loss): per thread C terms per pixel it visits, the wave
@@ -730,11 +775,19 @@ def test_mse_loss(dev, ops, C, total_pix):
         pred[:, C:] = NAN                  # pad lanes must not count
         target[:, C:] = NAN
         entries = ((True, C),) + (((False, 4),) if C == 4 else ())
+        by_c_entry = {}
         for general, c in entries:
             plain = {}
             for weight, accumulate, prior in ((1.0, 0, NAN), (0.25, 0, NAN), (0.25, 1, 3.0)):
                 dpred, loss = run_mse(ops, dev, pred, target, total_pix, c, coef, weight, accumulate, prior, general)
                 what = f'mse{"_c" if general else ""} C={C} pix={total_pix} grid={grid} w={weight} acc={accumulate}'
+                if general:
+                    by_c_entry[weight, accumulate] = (dpred, loss)
+                else:       # one kernel behind both entry points, and both reciprocals of 4 total_pix agree at these sizes
+                    dpred_c, loss_c = by_c_entry[weight, accumulate]
+                    assert same_bits(dpred, dpred_c), f'{what}: dpred differs from da_mse_loss_c at C = 4'
+                    assert struct.pack('<f', loss) == struct.pack('<f', loss_c), \
+                        f'{what}: loss {loss} differs from da_mse_loss_c at C = 4 ({loss_c})'
                 assert same_bits(dpred[:, C:], torch.zeros_like(dpred[:, C:])), f'{what}: pad lanes of dpred are not +0'
                 rd = d * f32(coef)
                 assert_sandwich('mse.dpred.c', dpred[:, :C], rd, U24 * rd.abs(), what + ' dpred')   # p - q, then * coef
@@ -752,15 +805,17 @@ def test_mse_loss(dev, ops, C, total_pix):
                     assert _margin('mse.loss.c', rel), f'{what}: loss {loss} vs {ref}: {rel:.3g} x depth {depth} x 2^-24'
 
 
-def test_mse_loss_c_rejects_misaligned(dev, ops):
+@pytest.mark.parametrize('entry', ['da_mse_loss', 'da_mse_loss_c'])
+def test_mse_loss_c_rejects_misaligned(dev, ops, entry):
     pred = torch.zeros(4 * 8 + 4, device=dev)
     dp = torch.full((4 * 8 + 8,), 7.0, device=dev, dtype=BF)
     loss, scratch = torch.full((1,), 5.0, device=dev), torch.zeros(1024, device=dev)
     from diffusion_amd.ops import _stream
+    channels = (3,) if entry == 'da_mse_loss_c' else ()
     for off_p, off_t, off_d in ((4, 0, 0), (0, 4, 0), (0, 0, 2)):
         with pytest.raises(RuntimeError, match='DA_ERR_SHAPE'):
-            ops._lib.call('da_mse_loss_c', pred.data_ptr() + off_p, pred.data_ptr() + off_t, dp.data_ptr() + off_d,
-                          loss.data_ptr(), scratch.data_ptr(), 4, 3, 1.0, 1.0, 0, _stream())
+            ops._lib.call(entry, pred.data_ptr() + off_p, pred.data_ptr() + off_t, dp.data_ptr() + off_d,
+                          loss.data_ptr(), scratch.data_ptr(), 4, *channels, 1.0, 1.0, 0, _stream())
     torch.cuda.synchronize()
     assert float(loss) == 5.0 and bool((dp == 7.0).all())
 

@@ -5,6 +5,7 @@ per cent, so numbers from different gpurun boxes are not comparable).
   python tools/lib_ab.py <old.so> tn [B]               weight-gradient GEMM at the U-Net's shapes (batch B, default 256)
   python tools/lib_ab.py <old.so> nt [B]               forward / dgrad GEMM (convs, linears with bias + residual, fused GEGLU)
   python tools/lib_ab.py <old.so> gn                   GroupNorm(+SiLU) forward / backward at the U-Net's shapes
+  python tools/lib_ab.py <old.so> pw                   the strided-map, noising and loss kernels of pointwise.hip, bit for bit
 With candidates, each is timed against <old.so>; without, the shipped library is the candidate.
 
 <old.so> is any earlier build, e.g.  git show <rev>:diffusion_amd/csrc/attention.hip > /tmp/a.hip ; hipcc ... -o tools/_ab/old.so
@@ -218,6 +219,83 @@ def run(old, new, what):
                   f'bwd {ba:7.1f} -> {bb:7.1f} us ({5 * nb / bb / 1e6:5.2f} TB/s, {100 * (ba / bb - 1):+5.1f} %)  '
                   f'rel y {rel(bufs[1]["y"], bufs[0]["y"]):.1e} dx {rel(bufs[1]["dx"], bufs[0]["dx"]):.1e}', flush=True)
             del x, dy, bufs
+    elif what == 'pw':
+        # the strided-map, noising and loss kernels of pointwise.hip.  Most of these launches take microseconds, so the
+        # launches per timed window are calibrated per row to ~30 ms of the old build (5 launches would time the clock)
+        bits = lambda t: t.view(torch.int16 if t.dtype == BF else torch.int32)   # noqa: E731
+        spread = {}
+
+        def row(op, label, call, outs):
+            """call(lib, o) launches on the output tensors o; outs = (the old build's, the new build's)"""
+            fa, fb = (lambda: call(old, outs[0])), (lambda: call(new, outs[1]))
+            fa(); fb(); torch.cuda.synchronize()
+            reps = max(5, min(20000, int(30e3 / max(timeit(fa, 20), 1e-3))))
+            ta, tb = ab(fa, fb, reps=reps, rounds=7)
+            equal = all(torch.equal(bits(x), bits(y)) for x, y in zip(*outs))
+            pct = 100 * (ta / tb - 1)
+            spread.setdefault(op, []).append(pct)
+            print(f'pw {op:14s} {label:28s}: {ta:8.2f} -> {tb:8.2f} us ({pct:+5.1f} %, {reps} launches / window)  '
+                  f'equal bits {equal}', flush=True)
+
+        def mat(M, Cc):
+            return torch.randn(M, Cc, device=dev).to(BF)
+
+        def two(*shape, dtype=BF):
+            return tuple([torch.empty(*shape, device=dev, dtype=dtype)] for _ in range(2))
+
+        def strided(name, ins, Cc):
+            """an entry point of the map: (pointer, ld) per operand, then M, C"""
+            flat = [v for t_ in ins for v in (t_.data_ptr(), t_.stride(0))]
+            return lambda lib, o: _ok(getattr(lib, name)(*flat, o[0].data_ptr(), o[0].stride(0), ins[0].shape[0], Cc, st))
+
+        def _ok(rc):
+            assert rc == 0, rc
+
+        for M, Cc in ((262144, 320), (65536, 640), (16384, 1280), (4096, 1280)):
+            a, b = mat(M, Cc), mat(M, Cc)
+            row('add', f'{M}x{Cc}', strided('da_add', (a, b), Cc), two(M, Cc))
+            row('copy2d', f'{M}x{Cc}', strided('da_copy2d', (a,), Cc), two(M, Cc))
+            if Cc == 640:     # a skip gradient: one operand is a column slice of the concat buffer's gradient
+                cat = mat(M, 2 * Cc)
+                row('add', f'{M}x{Cc} b = [:, {Cc}:] of {2 * Cc}', strided('da_add', (a, cat[:, Cc:]), Cc), two(M, Cc))
+                del cat
+            del a, b
+        x, dy = mat(256, 1280), mat(256, 1280)
+        row('silu_fwd', '256x1280', strided('da_silu_fwd', (x,), 1280), two(256, 1280))
+        row('silu_bwd', '256x1280', strided('da_silu_bwd', (x, dy), 1280), two(256, 1280))
+        x = mat(19712, 4096)
+        row('gelu_fwd', '19712x4096', strided('da_gelu_fwd', (x,), 4096), two(19712, 4096))
+        x = mat(19712, 3072)
+        row('quick_gelu_fwd', '19712x3072', strided('da_quick_gelu_fwd', (x,), 3072), two(19712, 3072))
+        del x, dy
+        for M, Cc in ((262144, 320), (65536, 640), (16384, 1280)):      # the shapes of tools/pw_bench.py
+            inner = 4 * Cc
+            proj, dout = mat(M, 2 * inner), mat(M, inner)
+            row('geglu_fwd', f'{M}x{inner}', strided('da_geglu_fwd', (proj,), inner), two(M, inner))
+            row('geglu_bwd', f'{M}x{inner}', strided('da_geglu_bwd', (proj, dout), inner), two(M, 2 * inner))
+            del proj, dout
+        betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, 1000, dtype=torch.float64) ** 2
+        ac = torch.cumprod(1 - betas, 0)
+        sa, s1 = ac.sqrt().float().to(dev), (1 - ac).sqrt().float().to(dev)
+        for B, side in ((256, 32), (64, 64)):
+            HW = side * side
+            x0, eps = torch.randn(B, 4, HW, device=dev), torch.randn(B, 4, HW, device=dev)
+            t = torch.randint(0, 1000, (B,), device=dev)
+            for v_pred in (0, 1):
+                outs = tuple([torch.empty(B * HW, 8, device=dev, dtype=BF), torch.empty(B * HW, 8, device=dev)] for _ in range(2))
+                row('add_noise', f'B={B} 4x{side}x{side} v_pred={v_pred}',
+                    lambda lib, o: _ok(lib.da_add_noise(x0.data_ptr(), eps.data_ptr(), t.data_ptr(), sa.data_ptr(), s1.data_ptr(),
+                                                        o[0].data_ptr(), o[1].data_ptr(), B, HW, v_pred, st)), outs)
+        pix = 262144
+        pred, target = torch.randn(pix, 8, device=dev), torch.randn(pix, 8, device=dev)
+        outs = tuple([torch.empty(pix, 8, device=dev, dtype=BF), torch.empty(1, device=dev), torch.empty(1024, device=dev)]
+                     for _ in range(2))
+        row('mse_loss', f'{pix} pixels',
+            lambda lib, o: _ok(lib.da_mse_loss(pred.data_ptr(), target.data_ptr(), o[0].data_ptr(), o[1].data_ptr(),
+                                               o[2].data_ptr(), pix, 2.0 / (4 * pix), 1.0, 0, st)), outs)
+        for op, pcts in spread.items():     # with the same build on both sides this is the op's noise
+            print(f'pw spread {op:14s}: new slower by at most {max(0.0, -min(pcts)):4.1f} %, largest |difference| '
+                  f'{max(abs(v) for v in pcts):4.1f} %', flush=True)
     else:
         raise SystemExit(__doc__)
 
