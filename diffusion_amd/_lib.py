@@ -65,11 +65,14 @@ SIGNATURES = {
     'da_mse_loss': [_fp, _fp, _vp, _fp, _fp, _l, _f, _f, _i, _vp],
     'da_mse_loss_c': [_fp, _fp, _vp, _fp, _fp, _l, _i, _f, _f, _i, _vp],
     'da_adamw': [_fp, _fp, _fp, _fp, _vp, _fp, _f, _l, _f, _f, _f, _f, _f, _i, _f, _vp],
+    'da_segment_sumsq': [_fp, _vp, _i, _vp, _i, _fp, _fp, _fp, _f, _f, _vp],
+    'da_segment_sumsq_scratch_floats': [_i],
+    'da_adamw_dev': [_fp, _fp, _fp, _fp, _vp, _fp, _f, _l, _f, _f, _f, _f, _f, _i, _fp, _vp],
     'da_cast_f32_bf16': [_fp, _vp, _l, _vp],
     'da_transpose_weight': [_vp, _vp, _i, _i, _i, _vp],
     'da_transpose_weights_batched': [_vp, _vp, _vp, _i, _i, _vp],
 }
-_RESTYPES = {'da_norm_scratch_floats': C.c_long}
+_RESTYPES = {'da_norm_scratch_floats': C.c_long, 'da_segment_sumsq_scratch_floats': C.c_long}
 
 _lib = None
 

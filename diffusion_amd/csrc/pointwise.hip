@@ -270,10 +270,21 @@ __global__ void mse_finalize_kernel(const float* partial, int n, float* loss, fl
   }
 }
 
-// ---- fused AdamW (torch.optim.AdamW semantics), flat buffers; writes the bf16 compute shadow
+// ---- fused AdamW (torch.optim.AdamW semantics), flat buffers; writes the bf16 compute shadow.  One kernel text, two
+// instantiations, so da_adamw and da_adamw_dev cannot drift: GS = float takes the gradient multiplier as an argument;
+// GS = const float* reads it from the device record of the gradient-norm pass (gradnorm.hip, DaGradStats as fp32 words:
+// [2] the multiplier, [3] 0.0 = a non-finite gradient: touch nothing).
+template <typename GS>
 __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, float ema_s,
                              long n, float lr, float b1, float b2, float eps, float wd, float inv_bc1,
-                             float inv_sqrt_bc2, float gscale) {
+                             float inv_sqrt_bc2, GS gs) {
+  float gscale;
+  if constexpr (__is_same(GS, float)) {
+    gscale = gs;
+  } else {
+    if (gs[3] == 0.f) return;
+    gscale = gs[2];
+  }
   GRID_STRIDE(i4, (n + 3) / 4) {
     long i = i4 * 4;
     if (i + 3 < n) {
@@ -551,9 +562,25 @@ extern "C" int da_adamw(float* p, const float* g, float* m, float* v, void* shad
     return DA_ERR_SHAPE;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(pw_blocks((n + 3) / 4)), dim3(PW_BLOCK), 0, s, p, g, m, v, (bf16*)shadow, ema,
-                     ema_smoothing, n,
+  hipLaunchKernelGGL(adamw_kernel<float>, dim3(pw_blocks((n + 3) / 4)), dim3(PW_BLOCK), 0, s, p, g, m, v, (bf16*)shadow,
+                     ema, ema_smoothing, n,
                      lr, beta1, beta2, eps, wd, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), grad_scale);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+extern "C" int da_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing,
+                            long n, float lr, float beta1, float beta2, float eps, float wd, int step, const float* stats,
+                            hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (n <= 0 || step <= 0 || !stats) return DA_ERR_SHAPE;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || ((uintptr_t)shadow & 7) ||
+      ((uintptr_t)stats & 3))
+    return DA_ERR_SHAPE;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adamw_kernel<const float*>, dim3(pw_blocks((n + 3) / 4)), dim3(PW_BLOCK), 0, s, p, g, m, v,
+                     (bf16*)shadow, ema, ema_smoothing, n, lr, beta1, beta2, eps, wd, (float)(1.0 / bc1),
+                     (float)(1.0 / sqrt(bc2)), stats);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -4,7 +4,8 @@ command-line overrides, ``_partial_`` / ``_recursive_``.  hydra-core and omegaco
 
 Targets are resolved through ``TARGET_ALIASES`` first so the reference's YAMLs run unmodified:
 ``diffusion.*`` -> ``diffusion_amd.*``, ``composer.Trainer`` -> the in-tree trainer, ``torch.optim.AdamW`` -> the
-fused HIP AdamW (when given U-Net parameters), observability callbacks/loggers -> no-ops."""
+fused HIP AdamW (when given U-Net parameters), ``GradientClipping`` / ``OptimizerMonitor`` -> the device-side norm pass,
+other observability callbacks/loggers and algorithms -> no-ops."""
 from __future__ import annotations
 
 import functools
@@ -19,6 +20,10 @@ TARGET_ALIASES = {
     'composer.optim.MultiStepWithWarmupScheduler': 'diffusion_amd.trainer.MultiStepWithWarmupScheduler',
     'composer.callbacks.speed_monitor.SpeedMonitor': 'diffusion_amd.trainer.SpeedMonitor',
     'composer.callbacks.SpeedMonitor': 'diffusion_amd.trainer.SpeedMonitor',
+    'composer.callbacks.OptimizerMonitor': 'diffusion_amd.trainer.OptimizerMonitor',
+    'composer.callbacks.optimizer_monitor.OptimizerMonitor': 'diffusion_amd.trainer.OptimizerMonitor',
+    'composer.algorithms.GradientClipping': 'diffusion_amd.algorithms.gradient_clipping.GradientClipping',
+    'composer.algorithms.gradient_clipping.GradientClipping': 'diffusion_amd.algorithms.gradient_clipping.GradientClipping',
     'torchmetrics.MeanSquaredError': 'diffusion_amd.models.composer_shim.MeanSquaredError',
     'torch.optim.AdamW': 'diffusion_amd.optim.FusedAdamW',
 }

@@ -136,6 +136,54 @@ class FlatParams:
         self.views.append((key, storage, fn))
 
 
+SUMSQ_CHUNK = 8192   # floats per chunk of da_segment_sumsq (DA_SUMSQ_CHUNK of include/diffusion_amd.h)
+
+
+class SumsqTables:
+    """Descriptor tables of da_segment_sumsq for a list of segments (pure host logic; ``to(device)`` uploads them once).
+
+    ``segments``: (offset, numel) runs of a flat fp32 buffer, in ascending offset order and disjoint.  Every segment is cut
+    into chunks of at most ``chunk`` floats; a chunk never crosses a segment, the chunks of a segment tile it without overlap,
+    and nothing outside a segment (an alignment gap) belongs to any chunk.
+      chunks   [(off, n, seg)]                 packed '<qii'
+      segs     [(first_chunk, n_chunks)]       packed '<ii'
+      extent   one past the last float any chunk reads (the kernel trusts the tables: ops.segment_sumsq checks the buffer)"""
+
+    def __init__(self, segments, chunk: int = SUMSQ_CHUNK):
+        self.chunk = int(chunk)
+        self.chunks, self.segs = [], []
+        end = 0
+        for s, (off, numel) in enumerate(segments):
+            off, numel = int(off), int(numel)
+            if numel <= 0 or off < end:
+                raise ValueError(f'segment {s}: (offset {off}, numel {numel}) must be non-empty, ascending and disjoint')
+            self.segs.append((len(self.chunks), -(-numel // self.chunk)))
+            for c in range(0, numel, self.chunk):
+                self.chunks.append((off + c, min(self.chunk, numel - c), s))
+            end = off + numel
+        if not self.segs:
+            raise ValueError('no segments')
+        self.extent = end
+        self.chunk_desc = self.seg_desc = None
+
+    def pack(self):
+        import struct
+        return (b''.join(struct.pack('<qii', *c) for c in self.chunks), b''.join(struct.pack('<ii', *s) for s in self.segs))
+
+    def to(self, device):
+        cb, sb = self.pack()
+        self.chunk_desc = torch.frombuffer(bytearray(cb), dtype=torch.uint8).to(device)
+        self.seg_desc = torch.frombuffer(bytearray(sb), dtype=torch.uint8).to(device)
+        return self
+
+
+def grad_segment_list(fp: 'FlatParams'):
+    """(names, offsets, numels) of the storages in flat order: the segments of the gradient-norm pass.  The 64-float
+    alignment gaps between storages belong to no segment (backward never writes them)."""
+    names = list(fp.storages)
+    return names, [fp.storages[n].off for n in names], [fp.storages[n].numel for n in names]
+
+
 def build_layout(cfg: UNetConfig):
     """Flat-buffer layout (pure host logic): storages in forward order + the diffusers-named views onto them."""
     class _S:
@@ -402,6 +450,14 @@ class UNetHIP(nn.Module):
             self._tdesc = torch.frombuffer(bytearray(b''.join(recs)), dtype=torch.uint8).to(self.device_)
             self._tdesc_n, self._tdesc_blocks = len(recs), first
         ops.transpose_weights_batched(self.shadow, self.shadow_t, self._tdesc, self._tdesc_n, self._tdesc_blocks)
+
+    def grad_segments(self):
+        """(names, offsets, numels, tables): the storages of the flat gradient buffer in flat order and the device tables of
+        the gradient-norm pass (ops.segment_sumsq), built once per layout like the transposed-shadow table above."""
+        if getattr(self, '_gseg', None) is None:
+            names, offs, numels = grad_segment_list(self.fp)
+            self._gseg = (names, offs, numels, SumsqTables(list(zip(offs, numels))).to(self.device_))
+        return self._gseg
 
     def zero_grad(self, set_to_none: bool = False):  # type: ignore[override]
         self.grad.zero_()

@@ -608,6 +608,49 @@ def adamw(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale, ema=N
               float(beta1), float(beta2), float(eps), float(wd), int(step), float(grad_scale), _stream())
 
 
+GRAD_STATS_WORDS = 8   # struct DaGradStats: fp32 sumsq, norm, grad_mult, finite; int32 skipped_steps; 3 reserved
+
+
+def segment_sumsq_scratch_floats(n_chunks: int) -> int:
+    return int(_lib.load().da_segment_sumsq_scratch_floats(int(n_chunks)))
+
+
+def segment_sumsq(x, tables, chunk_partials, seg_sumsq, stats=None, grad_scale=1.0, max_norm=0.0):
+    """Sum of squares of every segment of the flat fp32 buffer ``x`` (tables: models.unet.SumsqTables on the device) into
+    ``seg_sumsq`` [n_segs], and into ``stats`` (fp32[8], struct DaGradStats) the total, the global norm times grad_scale, the
+    gradient multiplier of torch's clip_grad_norm_ rule and the finite flag.  Enqueued on the current stream, no sync."""
+    nc, ns = len(tables.chunks), len(tables.segs)
+    if tables.chunk_desc is None or not tables.chunk_desc.is_cuda:
+        raise ValueError('segment_sumsq: tables not on the device (SumsqTables.to(device))')
+    if x.dtype != F32 or not x.is_contiguous() or not x.is_cuda or x.numel() < tables.extent:
+        raise ValueError(f'segment_sumsq: x must be a contiguous fp32 device buffer of >= {tables.extent} elements')
+    if seg_sumsq.dtype != F32 or not seg_sumsq.is_contiguous() or seg_sumsq.numel() < ns or not seg_sumsq.is_cuda:
+        raise ValueError(f'segment_sumsq: seg_sumsq must be contiguous fp32[>= {ns}] on the device')
+    if stats is not None and (stats.dtype != F32 or not stats.is_contiguous() or stats.numel() < GRAD_STATS_WORDS or not stats.is_cuda):
+        raise ValueError(f'segment_sumsq: stats must be contiguous fp32[{GRAD_STATS_WORDS}] on the device')
+    _lib.call('da_segment_sumsq', x.data_ptr(), tables.chunk_desc.data_ptr(), nc, tables.seg_desc.data_ptr(), ns,
+              _f32buf(chunk_partials, segment_sumsq_scratch_floats(nc), 'chunk_partials'), seg_sumsq.data_ptr(),
+              stats.data_ptr() if stats is not None else 0, float(grad_scale), float(max_norm), _stream())
+
+
+def adamw_dev(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, stats, ema=None, ema_smoothing=0.0):
+    """``adamw`` with the gradient multiplier read from ``stats[2]`` on the device; when ``stats[3] == 0`` (a non-finite
+    gradient) the kernel writes nothing.  ``step`` is the host's step number either way."""
+    n = p.numel()
+    for z in (p, g, m, v):
+        if z.dtype != F32 or not z.is_contiguous() or z.numel() != n:
+            raise ValueError('adamw_dev: fp32 contiguous flat buffers of equal size required')
+    if shadow.dtype != BF16 or shadow.numel() != n:
+        raise ValueError('adamw_dev: shadow')
+    if ema is not None and (ema.dtype != F32 or not ema.is_contiguous() or ema.numel() != n):
+        raise ValueError('adamw_dev: ema buffer')
+    if stats.dtype != F32 or not stats.is_contiguous() or stats.numel() < GRAD_STATS_WORDS or not stats.is_cuda:
+        raise ValueError(f'adamw_dev: stats must be contiguous fp32[{GRAD_STATS_WORDS}] on the device')
+    _lib.call('da_adamw_dev', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), shadow.data_ptr(),
+              ema.data_ptr() if ema is not None else 0, float(ema_smoothing), n, float(lr),
+              float(beta1), float(beta2), float(eps), float(wd), int(step), stats.data_ptr(), _stream())
+
+
 def cast_f32_bf16(src, dst):
     if src.dtype != F32 or dst.dtype != BF16 or src.numel() != dst.numel() or not src.is_contiguous():
         raise ValueError('cast: bad args')

@@ -2,8 +2,16 @@
 
 Stands where diffusion/train.py:33 instantiates ``torch.optim.AdamW`` from yamls/hydra-yamls/SD-2-base-256.yaml:55-58
 (lr 1e-4, weight_decay 0.01, torch-default betas/eps).  Same update rule as torch.optim.AdamW; additionally writes
-the bf16 compute shadow and refreshes the transposed (dgrad) shadow."""
+the bf16 compute shadow and refreshes the transposed (dgrad) shadow.
+
+Opt-in, on the device: clipping by the global gradient norm (``clip_max_norm``, torch.nn.utils.clip_grad_norm_'s rule) and a
+guard that skips the step when the gradient holds an inf or NaN (``guard_nonfinite``; the reference gets this from the
+GradScaler of its ``amp_fp16``).  Both run the segmented sum-of-squares pass over the flat gradient and hand AdamW its
+gradient multiplier and the skip flag in device memory - no host sync between backward and the update."""
 from __future__ import annotations
+
+import struct
+from typing import Optional
 
 import torch
 
@@ -13,7 +21,8 @@ from . import ops
 class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, params=None, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, unet=None):
+                 weight_decay: float = 1e-2, unet=None, clip_max_norm: Optional[float] = None,
+                 guard_nonfinite: bool = False):
         if unet is None:
             raise ValueError('FusedAdamW needs the UNetHIP that owns the flat parameter buffers (unet=...)')
         self.unet = unet
@@ -23,6 +32,62 @@ class FusedAdamW(torch.optim.Optimizer):
         self.ema = None            # flat fp32 EMA of the weights (set by algorithms.ema.EMA)
         self.ema_smoothing = 0.0
         self.ema_update_this_step = False
+        if clip_max_norm is not None and not clip_max_norm >= 0:
+            raise ValueError(f'clip_max_norm must be >= 0 (0 = no clipping), got {clip_max_norm}')
+        self.clip_max_norm = clip_max_norm      # None / 0: no clipping
+        self.guard_nonfinite = bool(guard_nonfinite)
+        self._gn = None                         # buffers of the norm pass (allocated on first use)
+        self._gn_fresh = False                  # the record describes the gradient as it stands (trainer: shared pass)
+        self._skipped_loaded = 0                # from a checkpoint, until the device record exists
+
+    # ---- gradient norm / clipping / non-finite guard -------------------------------------------------------------------
+    @property
+    def device_scaled(self) -> bool:
+        """True when step() takes its gradient multiplier from the device record (clipping or the guard is on).  The norm
+        needs every gradient final before any update, so step_range() slices are not available then."""
+        return bool(self.clip_max_norm) or self.guard_nonfinite
+
+    def _gn_buffers(self):
+        if self._gn is None:
+            from . import ops
+            u = self.unet
+            names, offs, numels, tables = u.grad_segments()
+            dev = u.grad.device
+            stats = torch.zeros(ops.GRAD_STATS_WORDS, device=dev, dtype=torch.float32)
+            if self._skipped_loaded:
+                stats[4:5].view(torch.int32).fill_(self._skipped_loaded)
+            self._gn = {'names': names, 'tables': tables, 'stats': stats,
+                        'seg': torch.zeros(len(names), device=dev, dtype=torch.float32),
+                        'partials': torch.zeros(ops.segment_sumsq_scratch_floats(len(tables.chunks)), device=dev,
+                                                dtype=torch.float32)}
+        return self._gn
+
+    @torch.no_grad()
+    def compute_grad_stats(self):
+        """The norm pass over ``unet.grad`` as it stands (three launches on the current stream, no sync): per-storage sums of
+        squares, and the device record {sumsq, norm, multiplier, finite} for this step's grad_scale and clip_max_norm.  The
+        next step() reuses the record instead of running the pass again (the trainer's monitor and the clipper share it);
+        call it only once the gradient is final."""
+        gn = self._gn_buffers()
+        ops.segment_sumsq(self.unet.grad, gn['tables'], gn['partials'], gn['seg'], gn['stats'], self.grad_scale,
+                          float(self.clip_max_norm or 0.0))
+        self._gn_fresh = True
+
+    def last_grad_stats(self) -> dict:
+        """The device record of the last norm pass, read back (this call syncs; nothing else here does):
+        sumsq, norm (= sqrt(sumsq) * grad_scale, the norm BEFORE clipping), grad_mult, finite, skipped_steps."""
+        if self._gn is None:
+            return {'sumsq': 0.0, 'norm': 0.0, 'grad_mult': self.grad_scale, 'finite': True, 'skipped_steps': self._skipped_loaded}
+        sumsq, norm, mult, finite, skipped = struct.unpack('<ffffi', self._gn['stats'].cpu().numpy().tobytes()[:20])
+        return {'sumsq': sumsq, 'norm': norm, 'grad_mult': mult, 'finite': finite != 0.0, 'skipped_steps': skipped}
+
+    def last_segment_norms(self) -> dict:
+        """{storage name: sqrt(sumsq) * grad_scale} and 'global', from the last norm pass: one device-to-host copy."""
+        gn = self._gn_buffers()
+        host = torch.cat([gn['seg'], gn['stats'][:1]]).cpu().double().sqrt() * self.grad_scale
+        out = {n: float(v) for n, v in zip(gn['names'], host[:-1])}
+        out['global'] = float(host[-1])
+        return out
 
     # The update can be issued in slices as gradients become final (trainer + parallel.BucketedAllReducer hand over
     # [lo, hi) ranges back-to-front during the last microbatch's backward, on the reducer's side stream), so the
@@ -49,7 +114,28 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        """Update everything begin_step()/step_range() have not covered yet, then refresh the dgrad weight shadow."""
+        """Update everything begin_step()/step_range() have not covered yet, then refresh the dgrad weight shadow.
+
+        With clipping or the guard on: the norm pass over the whole gradient (unless compute_grad_stats() already ran on
+        it), then one AdamW launch over the whole buffer that reads its multiplier from the device.  On a non-finite
+        gradient that launch writes nothing: weights, moments, shadow and EMA keep their bits and the device counter
+        ``skipped_steps`` goes up by one.  The host step number (``unet.opt_step``, the bias correction) advances all the
+        same - the host does not know, and must not wait to know, whether the device skipped."""
+        if self.device_scaled:
+            if getattr(self, '_open', False):
+                raise RuntimeError('step_range() slices cannot be combined with clip_max_norm / guard_nonfinite')
+            if not self._gn_fresh:
+                self.compute_grad_stats()
+            self._gn_fresh = False
+            self.unet.opt_step += 1
+            g, u = self.param_groups[0], self.unet
+            ema = self.ema if (self.ema is not None and self.ema_update_this_step) else None
+            ops.adamw_dev(u.master, u.grad, u.exp_avg, u.exp_avg_sq, u.shadow, g['lr'], g['betas'][0], g['betas'][1],
+                          g['eps'], g['weight_decay'], u.opt_step, self._gn['stats'], ema=ema,
+                          ema_smoothing=self.ema_smoothing)
+            u.refresh_transposed()
+            return
+        self._gn_fresh = False
         if not getattr(self, '_open', False):
             self.begin_step()
         self.step_range(0, self._pending_hi)
@@ -67,6 +153,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.ema is not None:
             sd['ema'] = self.ema.detach().cpu().clone()
             sd['ema_smoothing'] = self.ema_smoothing
+        if self.device_scaled:
+            sd['skipped_steps'] = self.last_grad_stats()['skipped_steps']
         return sd
 
     def load_state_dict(self, sd):
@@ -79,3 +167,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if 'ema' in sd:
             self.ema = sd['ema'].to(device=u.master.device, dtype=u.master.dtype).clone()
             self.ema_smoothing = float(sd['ema_smoothing'])
+        if 'skipped_steps' in sd:   # absent from checkpoints written without clipping / the guard
+            self._skipped_loaded = int(sd['skipped_steps'])
+            if self._gn is not None:
+                self._gn['stats'][4:5].view(torch.int32).fill_(self._skipped_loaded)

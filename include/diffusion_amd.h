@@ -294,6 +294,47 @@ int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* lo
 int da_adamw(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing, long n,
              float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale, da_stream_t stream);
 
+/* The device record the gradient-norm pass writes and da_adamw_dev reads (8 words, 4-byte aligned):
+ *   sumsq          sum of squares of the raw buffer (all segments)
+ *   norm           sqrt(sumsq) * grad_scale: the global gradient norm (grad_scale = 1 / world: the buffer holds the rank sum)
+ *   grad_mult      the gradient multiplier AdamW is to use: grad_scale * min(1, max_norm / (norm + 1e-6)), which is
+ *                  torch.nn.utils.clip_grad_norm_'s rule; exactly grad_scale when max_norm <= 0 or norm <= max_norm
+ *                  (norm and grad_mult are worked out in fp64 from the fp64 total and rounded once; "norm <= max_norm" is
+ *                  decided on the fp32 norm stored here)
+ *   finite         1.0 when sumsq is finite, else 0.0 (da_adamw_dev then leaves every buffer untouched)
+ *   skipped_steps  incremented by one each time a pass finds sumsq non-finite; the owner zeroes it once */
+#define DA_SUMSQ_CHUNK 8192 /* floats per chunk of da_segment_sumsq: the host's chunk tables are cut to this */
+typedef struct DaGradStats {
+  float sumsq, norm, grad_mult, finite;
+  int skipped_steps;
+  int reserved[3];
+} DaGradStats;
+
+/* Sum of squares of every segment of a flat fp32 buffer, their total, and the clip coefficient / step guard derived from
+ * it (Composer's GradientClipping(clipping_type='norm'), OptimizerMonitor's l2_norm/grad metrics and the inf/NaN check of
+ * the reference's GradScaler, train.py:118-128 + SD-2-base-256.yaml:80-81).  Nothing returns to the host.
+ * A segment is a run (offset, numel) of x; the host cuts each into chunks of at most DA_SUMSQ_CHUNK floats that never cross
+ * a segment.  chunk_desc: n_chunks records {long off (floats from x), int n, int seg}, segment-major in offset order;
+ * seg_desc: n_segs records {int first_chunk, int n_chunks}.  Only words inside a chunk are read: whatever lies between
+ * segments (alignment gaps) never enters a sum.  Up to three launches on `stream`, no atomics:
+ *   1. chunk_partials[c] = fp32 sum of squares of chunk c (>= da_segment_sumsq_scratch_floats(n_chunks) floats);
+ *   2. seg_sumsq[s] = the segment's partials summed in fp64, stored as fp32;
+ *   3. stats (a DaGradStats, may be NULL: launch 3 is then left out) from the fp64 sum of seg_sumsq, grad_scale, max_norm.
+ * Every sum's order is a function of the tables alone: the result does not depend on the grid, on "reserve_cus" or on
+ * what else runs.  DA_ERR_SHAPE (nothing launched) for n_chunks <= 0, n_segs <= 0, a NULL table / output or x not 16-byte
+ * aligned.  The tables are trusted: the caller guarantees every chunk lies inside x. */
+int da_segment_sumsq(const float* x, const void* chunk_desc, int n_chunks, const void* seg_desc, int n_segs,
+                     float* chunk_partials, float* seg_sumsq, float* stats, float grad_scale, float max_norm,
+                     da_stream_t stream);
+long da_segment_sumsq_scratch_floats(int n_chunks);
+
+/* da_adamw with the gradient multiplier and a "skip this step" flag read from device memory: grad_scale = stats[2]
+ * (DaGradStats.grad_mult), and when stats[3] (finite) is 0 the kernel returns without writing p, m, v, shadow or ema.  The
+ * arithmetic is da_adamw's (one shared body).  `step` is the host's count and is used for the bias correction whether or
+ * not the device skips.  Same rejections as da_adamw, plus a NULL stats. */
+int da_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing, long n,
+                 float lr, float beta1, float beta2, float eps, float wd, int step, const float* stats, da_stream_t stream);
+
 int da_cast_f32_bf16(const float* src, void* dst, long n, da_stream_t stream);
 
 /* dst[c][T-1-t][n] = src[n][t][c]: the weight layout da_gemm_nt needs for dgrad */
