@@ -9,6 +9,8 @@ pixel models train on.  ``DDIMScheduler`` (models.py:89) carries what ``generate
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -70,6 +72,21 @@ class DDIMScheduler(DDPMScheduler):
 
     def scale_model_input(self, sample, timestep=None):
         return sample
+
+    def step_coefficients(self, timestep):
+        """``step`` as three Python floats (cx, cm, cn), computed in float64: prev_sample = cx * sample + cm * model_output
+        (+ cn * noise, 0 for eta = 0).  The step is linear in both for each prediction type; ``prediction_type`` and
+        ``num_inference_steps`` are read now, like ``step`` does.  What ``ops.sampler_step`` applies on the device."""
+        t = int(timestep)
+        prev_t = t - self.num_train_timesteps // self.num_inference_steps
+        ac_t = float(self.alphas_cumprod[t])
+        ac_prev = float(self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod)
+        a, s, A, S = math.sqrt(ac_t), math.sqrt(1 - ac_t), math.sqrt(ac_prev), math.sqrt(1 - ac_prev)
+        if self.prediction_type == 'v_prediction':
+            return A * a + S * s, S * a - A * s, 0.0
+        if self.prediction_type == 'sample':
+            return S / s, A - S * a / s, 0.0
+        return A / a, S - A * s / a, 0.0
 
     def step(self, model_output, timestep, sample, generator=None, **kw):
         t = int(timestep)

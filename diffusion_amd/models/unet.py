@@ -305,6 +305,14 @@ def build_layout(cfg: UNetConfig):
 
 
 
+class _NoTape:
+    """What the forward-only walk appends to: nothing is kept, so no entry keeps an activation alive."""
+
+    @staticmethod
+    def append(entry):
+        pass
+
+
 class UNetOutput(dict):
     """Supports both ``out['sample']`` (stable_diffusion.py:183) and ``out.sample`` (:367)."""
 
@@ -346,6 +354,8 @@ class UNetHIP(nn.Module):
         self.wgrad_stream = torch.cuda.Stream() if os.environ.get('DA_WGRAD_STREAM', '0') == '1' else None
         self._wgrad_defer = None   # (M, [(dy, x, gw, dbias), ...]) while _transformer_bwd collects its linear weight gradients
         self._tape = None
+        self._kv, self._record = None, True   # the forward-only walk of sampling sets these for its duration
+        self._ctx = self._tproj = None
         if init:
             self.reset_parameters(seed)
 
@@ -608,7 +618,7 @@ class UNetHIP(nn.Module):
             res = x
         y = out if out is not None else self._bf(M, cout)
         ops.gemm_nt(a2, conv2.w, y, g3, bias=self.V(p + '.conv2.bias').p, residual=res)
-        return y, (p, x, a1, st1, h1, a2, st2, B, H, W)
+        return y, ((p, x, a1, st1, h1, a2, st2, B, H, W) if self._record else None)
 
     def _resnet_bwd(self, saved, dout):
         p, x, a1, st1, h1, a2, st2, B, H, W = saved
@@ -669,8 +679,11 @@ class UNetHIP(nn.Module):
         n2, ln2 = self._ln_fwd(h1, tb + '.norm2')
         q2 = self._lin_fwd(n2, tb + '.attn2.to_q', bias=False)
         nk = self._ctx.shape[0] // B
-        kv2 = self._bf(B * nk, 2 * C)
-        ops.gemm_nt(self._ctx, self.M(tb + '.attn2.kv.weight').w, kv2, Geom.linear(B * nk))
+        if self._kv is not None:   # sampling: the context is the same at every step, projected once (project_context)
+            kv2 = self._kv[p]
+        else:
+            kv2 = self._bf(B * nk, 2 * C)
+            ops.gemm_nt(self._ctx, self.M(tb + '.attn2.kv.weight').w, kv2, Geom.linear(B * nk))
         o2 = self._bf(M, C)
         l2 = self._f32(B * heads * HW)
         ops.attn_fwd(q2, kv2[:, :C], kv2[:, C:], o2, l2, B, heads, HW, nk, 0.125)
@@ -686,6 +699,8 @@ class UNetHIP(nn.Module):
             ops.geglu_fwd(f, gg)
         h3 = self._lin_fwd(gg, tb + '.ff.net.2', residual=h2)
         y = self._lin_fwd(h3, p + '.proj_out', out=out, residual=x)
+        if not self._record:
+            return y, None
         saved = (p, x, gst, g, h0, ln1, n1, qkv, o1, l1, h1, ln2, n2, q2, kv2, o2, l2, h2, ln3, n3, f, gg, h3, B, H, W,
                  heads)
         return y, saved
@@ -751,16 +766,49 @@ class UNetHIP(nn.Module):
     # ------------------------------------------------------------------------------------------
     # whole network
     # ------------------------------------------------------------------------------------------
-    def forward_features(self, xt8: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, B: int, S: int):
+    def forward_features(self, xt8: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, B: int, S: int, kv=None,
+                         record: bool = True):
         """xt8: [B*S*S, 8] bf16 NHWC(8) noised inputs; t: [B] int64 (discrete steps) or fp32 (continuous time);
         ctx: [B*77, ctx_dim] bf16.  Returns pred [B*S*S, 8] fp32 (channels out_channels..7 are zero) and records
-        everything backward needs."""
+        everything backward needs.
+
+        The sampling form: ``kv`` (``project_context(ctx)``) replaces the 16 cross-attention K/V GEMMs, and with
+        ``record=False`` nothing is kept for a backward - no tape, a block's intermediates die with the block and a concat
+        buffer with the up-path stage that reads it - so the walk peaks far below the training forward.  The launches
+        and their inputs are the same, hence the same prediction bit for bit."""
+        if kv is None and record:
+            return self._walk(xt8, t, ctx, B, S)
+        if kv is not None and record:
+            raise ValueError('forward_features: kv is for the forward-only walk (backward needs the projections it made)')
+        keep = (self._ctx, self._tproj)   # a recorded forward may be waiting for its backward
+        self._kv, self._record = kv, False
+        try:
+            return self._walk(xt8, t, ctx, B, S)
+        finally:
+            self._kv, self._record = None, True
+            self._ctx, self._tproj = keep
+
+    def project_context(self, ctx: torch.Tensor):
+        """The cross-attention K/V of every transformer block for ``ctx`` ([B*77, ctx_dim] bf16, ``prepare_ctx``): block
+        prefix -> [B*77, 2 C] bf16, by the GEMM ``_transformer_fwd`` runs.  For the forward-only walk of one ``sample()``
+        call; never cached across calls, the weights change between evals."""
+        kv = {}
+        for key in self._mats:
+            if key.endswith('.attn2.kv.weight'):
+                m = self.M(key)
+                out = self._bf(ctx.shape[0], m.N)
+                ops.gemm_nt(ctx, m.w, out, Geom.linear(ctx.shape[0]))
+                kv[key[:-len('.transformer_blocks.0.attn2.kv.weight')]] = out
+        return kv
+
+    def _walk(self, xt8, t, ctx, B, S):
         cfg = self.cfg
         boc = cfg.block_out_channels
         n = len(boc)
+        record = self._record
         self._ensure_scratch(B, S)
         self._ctx = ctx
-        tape: List[Tuple[str, tuple]] = []
+        tape = [] if record else _NoTape()   # List[Tuple[str, tuple]]
         # ---- timestep embedding MLP + all 22 time_emb_proj in one GEMM
         te0 = self._bf(B, boc[0])
         if t.dtype == F32:
@@ -776,7 +824,9 @@ class UNetHIP(nn.Module):
         self._tproj = self._bf(B, self.tproj_total)
         ops.gemm_nt(tembs, self.M('time_emb_proj_all.weight').w, self._tproj, Geom.linear(B),
                     bias=self.V('time_emb_proj_all.bias').p)
-        self._temb_saved = (te0, te1, te1s, temb, tembs)
+        if record:
+            self._temb_saved = (te0, te1, te1s, temb, tembs)
+        del te0, te1, te1s, temb, tembs
 
         # ---- concat buffers of the up path, allocated when their skip half is produced
         res = [S >> i for i in range(n)]
@@ -847,6 +897,8 @@ class UNetHIP(nn.Module):
                 else:
                     h, sv = self._resnet_fwd(p, cat, B, r, r, out=nxt)
                     tape.append(('resnet', sv))
+                if not record:
+                    cats[s] = cat = None   # consumed
                 s -= 1
             if i < n - 1:
                 key = f'up_blocks.{i}.upsamplers.0.conv'
@@ -857,6 +909,8 @@ class UNetHIP(nn.Module):
         a, st = self._gn_fwd(h, 'conv_norm_out', B, S * S, cfg.norm_eps, 1)
         pred = torch.empty(B * S * S, 8, device=self.device_, dtype=F32)
         ops.gemm_nt(a, self.M('conv_out.weight').w, pred, Geom.conv(B, S, S), bias=self.V('conv_out.bias').p)
+        if not record:
+            return pred
         tape.append(('out', (h, a, st, B, S)))
         self._tape = tape
         self._cats = cats

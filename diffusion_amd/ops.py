@@ -560,6 +560,37 @@ def image_ingest(raw, off, hw, R, out, kind, host=None):
     _lib.call('da_image_ingest', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, R, out.data_ptr(), int(kind), _stream())
 
 
+def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copies=1):
+    """One sampling step after the U-Net call (``da_sampler_step``): guidance, the scheduler update with the device
+    coefficients ``coef`` = {cx, cm, cn, guidance} and the next U-Net input.
+
+    pred fp32 [(2 if cfg else 1) * npix, 8]; x / x_out fp32 [npix, 8] (x_out may be x); noise None or fp32 NCHW
+    [B, C, H, W] with B * H * W = npix; xt_out None or bf16 [copies * npix, 8]."""
+    C, copies, cfg = int(C), int(copies), bool(cfg)
+    if not 1 <= C <= 8 or copies not in (1, 2):
+        raise ValueError(f'sampler_step: C = {C} (1..8), copies = {copies} (1 or 2)')
+    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
+        raise ValueError('sampler_step: x must be [npix, 8]')
+    npix = x.shape[0]
+    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (x_out, npix, 'x_out')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
+            raise ValueError(f'sampler_step: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 4 or coef.data_ptr() % 16:
+        raise ValueError('sampler_step: coef must be 4 contiguous fp32 on the device, 16-byte aligned')
+    HW = npix
+    if noise is not None:
+        if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
+                or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
+            raise ValueError(f'sampler_step: noise must be a contiguous fp32 [B, {C}, H, W] device tensor over {npix} pixels')
+        HW = noise.shape[2] * noise.shape[3]
+    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
+                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
+        raise ValueError(f'sampler_step: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    _lib.call('da_sampler_step', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
+              coef.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg),
+              copies, _stream())
+
+
 def add_noise(x0, eps, t, sqrt_ac, sqrt_1mac, xt, target, v_pred):
     B = x0.shape[0]
     HW = x0.shape[2] * x0.shape[3]

@@ -56,6 +56,30 @@ class ContinuousTimeScheduler:
     def scale_model_input(self, model_input, t):
         return model_input
 
+    def step_coefficients(self, timestep):
+        """``step`` as three Python floats (cx, cm, cn), computed in float64: x_prev = cx * model_input + cm * model_output
+        + cn * noise, noise the SDE's standard normal draw (cn = 0 for the ODE).  ``prediction_type``, ``use_ode`` and the
+        number of inference steps are read now, like ``step`` does.  What ``ops.sampler_step`` applies on the device."""
+        t = float(timestep)
+        if t == 0:
+            return 1.0, 0.0, 0.0
+        beta, s, c = (float(v) for v in self.schedule_function(np.float64(t)))
+        dt = self.t_max / self.timesteps.shape[0]
+        if self.prediction_type == 'sample':          # x_0 = p * model_input + q * model_output
+            p, q = 0.0, 1.0
+        elif self.prediction_type == 'epsilon':
+            p, q = 1.0 / c, -s / c
+        elif self.prediction_type == 'v_prediction':
+            p, q = c, -s
+        else:
+            raise ValueError(
+                f'prediction type must be one of sample, epsilon, or v_prediction. Got {self.prediction_type}')
+        h = 0.5 * beta * dt
+        k = h if self.use_ode else beta * dt           # the weight of the score term
+        cx = 1.0 + h - k * (1.0 - c * p) / (s * s)
+        cm = k * c * q / (s * s)
+        return cx, cm, 0.0 if self.use_ode else float(np.sqrt(beta * dt))
+
     def step(self, model_output, t, model_input, generator=None):
         """One step t -> t - t_max / num_inference_timesteps.  The SDE's noise term is drawn from torch's global generator
         (``torch.randn_like``), as the reference does; ``generator`` is accepted for the diffusers call surface."""

@@ -264,6 +264,21 @@ int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f
                     const float* sqrt_1mac, void* xt, float* target, int B, int C, int HW, int target_kind,
                     da_stream_t stream);
 
+/* One denoising step of generate() after the U-Net call: classifier-free guidance, the scheduler update and the next U-Net
+ * input.  Every step of DDIMScheduler (eta = 0) and ContinuousTimeScheduler is linear in (sample, model output, noise
+ * draw); step_coefficients() of the schedulers gives the three coefficients.
+ *   pred   fp32 [(cfg ? 2 : 1) * npix][8], forward_features' output; with cfg rows [0, npix) are the unconditional half and
+ *          rows [npix, 2 npix) the conditional half (the torch.cat([uncond, text]) order of generate());
+ *   x      fp32 [npix][8], the sampler's state in NHWC-8; x_out the same shape, may be x itself;
+ *   noise  NULL, or fp32 NCHW [npix / HW][C][HW] (the Euler-Maruyama draw, in the layout da_add_noise reads);
+ *   coef   DEVICE pointer to four floats {cx, cm, cn, guidance}: the launch can sit in a captured graph;
+ *   xt_out NULL, or bf16 [copies * npix][8]: bf16(x_out) written `copies` (1 or 2) times, the next U-Net input.
+ * Per pixel and channel c < C: m = cfg ? pu + g (pt - pu) : p, x_out = cx x + cm m (+ cn z) in fp32.  Channels C..7 of
+ * both outputs are exactly 0 whatever the inputs hold there.  DA_ERR_SHAPE for C outside 1..8, copies outside {1, 2},
+ * npix <= 0 or no multiple of HW, a NULL pred / x / coef / x_out, or a pointer that is not 16-byte aligned. */
+int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, void* xt_out,
+                    long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+
 /* LargestCenterSquare(R) + ToTensor + Normalize(0.5,0.5) of B packed RGB uint8 images (transforms.py:9-21, laion.py:159-164):
  * PIL's antialiased bilinear resize of the shorter side to R (the longer one to floor(R*long/short)), the centre crop with
  * its origin rounded half to even, then v / 127.5 - 1.  src: tightly packed HWC images (row stride 3*w); off[b]: byte offset
