@@ -25,6 +25,8 @@ TARGET_ALIASES = {
     'composer.algorithms.GradientClipping': 'diffusion_amd.algorithms.gradient_clipping.GradientClipping',
     'composer.algorithms.gradient_clipping.GradientClipping': 'diffusion_amd.algorithms.gradient_clipping.GradientClipping',
     'torchmetrics.MeanSquaredError': 'diffusion_amd.models.composer_shim.MeanSquaredError',
+    'torchmetrics.multimodal.clip_score.CLIPScore': 'diffusion_amd.metrics.clip_score.CLIPScore',
+    'torchmetrics.multimodal.CLIPScore': 'diffusion_amd.metrics.clip_score.CLIPScore',
     'torch.optim.AdamW': 'diffusion_amd.optim.FusedAdamW',
 }
 TARGET_PREFIX_ALIASES = [

@@ -31,6 +31,12 @@ CLIP_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, 
                      max_position_embeddings=77, hidden_act='quick_gelu', layer_norm_eps=1e-5, projection_dim=768,
                      pad_token_id=1, bos_token_id=0, eos_token_id=2)
 
+# its published vision configuration (the image tower of the CLIP score): ViT-L/14 at 224, 257 tokens of width 1024
+CLIP_L14_VISION = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
+                       patch_size=14, hidden_act='quick_gelu', layer_norm_eps=1e-5, projection_dim=768)
+# CLIPImageProcessor's published per-channel mean and std for it (the shortest edge / crop is the image_size above)
+CLIP_L14_PREPROCESS = dict(image_mean=(0.48145466, 0.4578275, 0.40821073), image_std=(0.26862954, 0.26130258, 0.27577711))
+
 
 def build_clip_text_encoder(local_dir: Optional[str] = None, dtype=torch.float32, **overrides):
     """CLIP ViT-L/14 text encoder: strictly loaded from ``local_dir`` when it is a directory (every weight must be

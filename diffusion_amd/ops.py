@@ -560,6 +560,59 @@ def image_ingest(raw, off, hw, R, out, kind, host=None):
     _lib.call('da_image_ingest', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, R, out.data_ptr(), int(kind), _stream())
 
 
+CLIP_MAX_PATCH, CLIP_MAX_SIZE = 32, 448   # da_clip_preprocess: one block stages a P x P patch
+_CLIP_TABLES = {}   # (H, W, R, device) -> (xtab, ytab) int32 on the device
+
+
+def clip_patch_cols(P: int) -> int:
+    """columns of the patch matrix: 3 * P * P rounded up to the multiple of 8 da_gemm_nt needs (592 for P = 14)"""
+    return (3 * P * P + 7) // 8 * 8
+
+
+def clip_preprocess(images, R, P, out, kind, mean, std):
+    """``CLIPImageProcessor`` of uint8 [B, 3, H, W] device images (``da_clip_preprocess``): Pillow's bicubic resize of the
+    shorter side to R, centre crop, / 255, normalise.  out: kind 0 the patch matrix bf16 [B * ((R/P)**2 + 1), clip_patch_cols(P)]
+    with zero class-token rows, kind 1 ``pixel_values`` fp32 [B, 3, R, R].  The integer tap tables come from
+    ``metrics.clip_preprocess`` and are uploaded once per image size."""
+    from .metrics.clip_preprocess import tables_for
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 \
+            or images.shape[1] != 3 or not images.is_contiguous() or images.shape[0] < 1:
+        raise ValueError('clip_preprocess: images must be a contiguous uint8 [B, 3, H, W] device tensor')
+    B, _, H, W = images.shape
+    R, P = int(R), int(P)
+    if not (1 <= P <= CLIP_MAX_PATCH and P <= R <= CLIP_MAX_SIZE and R % P == 0):
+        raise ValueError(f'clip_preprocess: R = {R}, P = {P} (P <= {CLIP_MAX_PATCH}, R <= {CLIP_MAX_SIZE}, R % P == 0)')
+    if not (1 <= H <= IMAGE_INGEST_MAX_SIDE and 1 <= W <= IMAGE_INGEST_MAX_SIDE):
+        raise ValueError(f'clip_preprocess: image sides must be in 1..{IMAGE_INGEST_MAX_SIDE}')
+    if kind not in (0, 1):
+        raise ValueError(f'clip_preprocess: unknown out kind {kind!r} (0: bf16 patch matrix, 1: fp32 pixel_values)')
+    dt, shape, align = ((BF16, (B * ((R // P) ** 2 + 1), clip_patch_cols(P)), 16), (F32, (B, 3, R, R), 4))[kind]
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dt or not out.is_contiguous() \
+            or tuple(out.shape) != shape or out.data_ptr() % align:
+        raise ValueError(f'clip_preprocess: out must be a contiguous {dt} device tensor {shape}, {align}-byte aligned')
+    key = (H, W, R, images.device)
+    if key not in _CLIP_TABLES:
+        _CLIP_TABLES[key] = tuple(torch.from_numpy(t.copy()).to(images.device) for t in tables_for(H, W, R))
+    xtab, ytab = _CLIP_TABLES[key]
+    f3 = ctypes.c_float * 3
+    _lib.call('da_clip_preprocess', images.data_ptr(), B, H, W, R, P, xtab.data_ptr(), xtab.shape[1], ytab.data_ptr(),
+              ytab.shape[1], f3(*map(float, mean)), f3(*map(float, std)), out.data_ptr(), int(kind), _stream())
+    return out
+
+
+def clip_score(img, txt, scores, state):
+    """``da_clip_score``: scores[i] = 100 cos(img_i, txt_i); state[0] += their sum (index order), state[1] += B.  img / txt
+    fp32 [B, D] device matrices with unit column stride (any row stride); scores fp32 [B]; state fp32 [2]."""
+    for z, nm in ((img, 'img'), (txt, 'txt')):
+        if z.dim() != 2 or z.dtype != F32 or not z.is_cuda or z.stride(1) != 1 or z.shape != img.shape:
+            raise ValueError(f'clip_score: {nm} must be an fp32 [B, D] device matrix with unit column stride')
+    B, D = img.shape
+    if B < 1 or D < 1:
+        raise ValueError('clip_score: empty batch')
+    _lib.call('da_clip_score', img.data_ptr(), max(img.stride(0), D), txt.data_ptr(), max(txt.stride(0), D), B, D,
+              _vec(scores, B, 'scores'), _vec(state, 2, 'state'), _stream())
+
+
 def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copies=1):
     """One sampling step after the U-Net call (``da_sampler_step``): guidance, the scheduler update with the device
     coefficients ``coef`` = {cx, cm, cn, guidance} and the next U-Net input.

@@ -369,8 +369,10 @@ class Trainer:
         block's `eval_interval` / `eval_subset_num_batches`): every batch of ``eval_dataloader`` goes through
         ``model.eval_forward`` and every validation metric through ``model.update_metric`` (stable_diffusion.py:189-257); the
         metric states are summed over the ranks (squared-error sum and count, as torchmetrics' dist_reduce_fx="sum" does) and
-        logged as ``metrics/eval/<name>``.  Image-generation metrics (FID / CLIP score: val_guidance_scales) need the
-        evaluation datasets and Inception / CLIP weights that are out of scope; with no eval dataloader this returns {}."""
+        logged as ``metrics/eval/<name>``.  A ``CLIPScore`` among the validation metrics (metrics/clip_score.py) is fed the
+        images ``eval_forward`` generates per entry of ``val_guidance_scales`` and reduces its own two-float state over the
+        ranks in ``compute()``; FID / Inception score need a network whose op set is not on the HIP path and stay out of
+        scope.  With no eval dataloader this returns {}."""
         if self.eval_dataloader is None:
             return {}
         model = self.model

@@ -350,6 +350,30 @@ long da_segment_sumsq_scratch_floats(int n_chunks);
 int da_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing, long n,
                  float lr, float beta1, float beta2, float eps, float wd, int step, const float* stats, da_stream_t stream);
 
+/* The reference's CLIPImageProcessor (scripts/fid-clip-evaluation.py: torchmetrics CLIPScore's processor) on planar uint8
+ * images src [B, 3, H, W], all of one size: PIL's 8-bit bicubic resize of the shorter side to R, the centre crop to R x R,
+ * * 1/255 and (x - mean[c]) / std[c] (mean, std: 3 HOST floats each).  The resampling is Pillow's integer arithmetic: the
+ * host passes one coefficient table per axis, xtab [R][xld] / ytab [R][yld] int32 on the device, row i = {lo, count,
+ * k[count]} for cropped output index i: first source index, tap count and the 22-bit fixed-point weights.  One pass is
+ * clamp((2^21 + sum k * v) >> 22, 0, 255) in int32, horizontal first, rounded to a uint8 level between the passes.  lo and
+ * count are clamped to the image and to the row length before use, so no table makes the kernel read outside src.
+ *   out_kind 0: the patch matrix bf16 [B * (Np + 1)][Kp], Np = (R / P)^2, Kp = 3 P P rounded up to a multiple of 8; row
+ *               b (Np + 1) is the class-token slot (zeros), row b (Np + 1) + 1 + py (R / P) + px, column c P P + iy P + ix is
+ *               pixel (c, py P + iy, px P + ix); pad columns are zeros.  Every element is written exactly once.
+ *   out_kind 1: the reference's pixel_values, fp32 [B, 3, R, R].
+ * DA_ERR_SHAPE (nothing launched) for R % P != 0, P > 32, R > 448, sides outside 1..65535, xld / yld < 3, a NULL pointer
+ * or out not 16-byte (kind 0) / 4-byte (kind 1) aligned. */
+int da_clip_preprocess(const unsigned char* src, int B, int H, int W, int R, int P, const int* xtab, int xld,
+                       const int* ytab, int yld, const float* mean, const float* std, void* out, int out_kind,
+                       da_stream_t stream);
+
+/* CLIP score of B (image, text) embedding pairs, fp32 rows of D values with leading dimensions ldi / ldt:
+ * scores[i] = 100 * dot(a_i, b_i) / (|a_i| |b_i|) (no epsilon, no per-sample clamp: torchmetrics clamps the mean), then
+ * state[0] += the scores summed in index order and state[1] += B.  One workgroup, every reduction in a fixed order: two runs
+ * on the same inputs are bit-identical.  Nothing returns to the host. */
+int da_clip_score(const float* img, long ldi, const float* txt, long ldt, int B, int D, float* scores, float* state,
+                  da_stream_t stream);
+
 int da_cast_f32_bf16(const float* src, void* dst, long n, da_stream_t stream);
 
 /* dst[c][T-1-t][n] = src[n][t][c]: the weight layout da_gemm_nt needs for dgrad */
