@@ -16,6 +16,11 @@
 // (y, x) adds the rows of the chunk that fall into its vertical window.  Tap counts are loop bounds, not array sizes.
 // The horizontal pass is shared by the 16 rows of the tile; vertically adjacent tiles repeat the rows their windows share
 // ((16 + 2) / 16 of the minimum when downscaling).  Every read is at row lo..hi-1 < h, column lo..hi-1 < w of its own image.
+//
+// Rectangular targets.  The kernel takes the target as Rh rows x Rw columns and resizes to COVER it: the axis whose scale
+// factor is the larger one lands exactly on its target extent (w Rh <= h Rw: nw = Rw, nh = floor(Rw h / w); else nh = Rh,
+// nw = floor(Rh w / h)), so nw >= Rw and nh >= Rh and the centre crop lies inside the resized image.  At Rh == Rw the test
+// is w <= h and the rule is LargestCenterSquare's: da_image_ingest is the same kernel with Rh = Rw = R.
 #include "common.hpp"
 #include "diffusion_amd.h"
 
@@ -47,24 +52,26 @@ DEVINL void axis_setup(int n_in, int n_out, int i, int* lo_, int* hi_, int* num_
 
 __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const unsigned char* __restrict__ src,
                                                                           const long long* __restrict__ off,
-                                                                          const int* __restrict__ hw, int R, int tiles,
+                                                                          const int* __restrict__ hw, int Rh, int Rw,
+                                                                          int tiles_y, int tiles_x,
                                                                           void* __restrict__ out, int kind) {
   __shared__ int s_lo[2][IMG_TILE], s_hi[2][IMG_TILE], s_num[2][IMG_TILE];
   __shared__ double s_inv[2][IMG_TILE];
   __shared__ float s_row[IMG_TILE][IMG_TILE][3];
   const int t = threadIdx.x;
-  const int b = blockIdx.x / (tiles * tiles), tile = blockIdx.x - b * (tiles * tiles);
-  const int ty0 = (tile / tiles) * IMG_TILE, tx0 = (tile % tiles) * IMG_TILE;
+  const int b = blockIdx.x / (tiles_y * tiles_x), tile = blockIdx.x - b * (tiles_y * tiles_x);
+  const int ty0 = (tile / tiles_x) * IMG_TILE, tx0 = (tile % tiles_x) * IMG_TILE;
   const int h = hw[2 * b], w = hw[2 * b + 1];
   if (h < 1 || w < 1 || h > IMG_MAX_SIDE || w > IMG_MAX_SIDE) return;   // uniform over the block, before any barrier
-  // geometry: shorter side -> R, the longer one floor(R * long / short); crop origin rounded half to even
-  const int new_long = (int)((long long)R * (w > h ? w : h) / (w > h ? h : w));
-  const int nw = w <= h ? R : new_long, nh = w <= h ? new_long : R;
-  const int qy = (nh - R) >> 1, qx = (nw - R) >> 1;
-  const int top = ((nh - R) & 1) ? qy + (qy & 1) : qy, left = ((nw - R) & 1) ? qx + (qx & 1) : qx;
+  // geometry: resize to cover Rh x Rw (the tighter axis lands on its target, the other one is floored); crop origin rounded
+  // half to even.  w * Rh, h * Rw <= 65535 * 4096 < 2^31.
+  const bool fit_w = w * Rh <= h * Rw;
+  const int nw = fit_w ? Rw : (int)((long long)Rh * w / h), nh = fit_w ? (int)((long long)Rw * h / w) : Rh;
+  const int qy = (nh - Rh) >> 1, qx = (nw - Rw) >> 1;
+  const int top = ((nh - Rh) & 1) ? qy + (qy & 1) : qy, left = ((nw - Rw) & 1) ? qx + (qx & 1) : qx;
   if (t < 2 * IMG_TILE) {
-    const int a = t >> 4, j = t & (IMG_TILE - 1);   // a = 0: columns, 1: rows; indices past R repeat the last one
-    const int i = a ? min(ty0 + j, R - 1) + top : min(tx0 + j, R - 1) + left;
+    const int a = t >> 4, j = t & (IMG_TILE - 1);   // a = 0: columns, 1: rows; indices past the target repeat the last one
+    const int i = a ? min(ty0 + j, Rh - 1) + top : min(tx0 + j, Rw - 1) + left;
     axis_setup(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
   }
   __syncthreads();
@@ -106,7 +113,7 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
     __syncthreads();
   }
   const int Y = ty0 + y, X = tx0 + x;
-  if (Y >= R || X >= R) return;
+  if (Y >= Rh || X >= Rw) return;
   const double k = s_inv[1][y] * (1.0 / 127.5);   // ToTensor (/255) and Normalize(0.5, 0.5): v / 127.5 - 1
   const float o0 = (float)(acc0 * k - 1.0), o1 = (float)(acc1 * k - 1.0), o2 = (float)(acc2 * k - 1.0);
   if (kind == 0) {
@@ -114,29 +121,40 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
     o[0] = f2bf(o0);
     o[1] = f2bf(o1);
     o[2] = f2bf(o2);
-    st8(static_cast<bf16*>(out) + (((long)b * R + Y) * R + X) * 8, o);
+    st8(static_cast<bf16*>(out) + (((long)b * Rh + Y) * Rw + X) * 8, o);
   } else {
-    float* of = static_cast<float*>(out) + ((long)b * 3 * R + Y) * R + X;
+    float* of = static_cast<float*>(out) + ((long)b * 3 * Rh + Y) * Rw + X;
     of[0] = o0;
-    of[(long)R * R] = o1;
-    of[2L * R * R] = o2;
+    of[(long)Rh * Rw] = o1;
+    of[2L * Rh * Rw] = o2;
   }
+}
+
+int launch_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
+                  int out_kind, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B < 1 || Rh < 1 || Rh > 4096 || Rw < 1 || Rw > 4096 || (out_kind != 0 && out_kind != 1) || !src || !off || !hw ||
+      !out)
+    return DA_ERR_SHAPE;
+  if (out_kind == 0 && ((uintptr_t)out & 15)) return DA_ERR_SHAPE;
+  if (out_kind == 1 && ((uintptr_t)out & 3)) return DA_ERR_SHAPE;
+  const int tiles_y = (Rh + IMG_TILE - 1) / IMG_TILE, tiles_x = (Rw + IMG_TILE - 1) / IMG_TILE;
+  const long blocks = (long)B * tiles_y * tiles_x;
+  if (blocks > 0x7fffffffL) return DA_ERR_SHAPE;
+  hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, Rh, Rw,
+                     tiles_y, tiles_x, out, out_kind);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
 }
 
 }  // namespace
 
 extern "C" int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out,
                                int out_kind, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (B < 1 || R < 1 || R > 4096 || (out_kind != 0 && out_kind != 1) || !src || !off || !hw || !out)
-    return DA_ERR_SHAPE;
-  if (out_kind == 0 && ((uintptr_t)out & 15)) return DA_ERR_SHAPE;
-  if (out_kind == 1 && ((uintptr_t)out & 3)) return DA_ERR_SHAPE;
-  const int tiles = (R + IMG_TILE - 1) / IMG_TILE;
-  const long blocks = (long)B * tiles * tiles;
-  if (blocks > 0x7fffffffL) return DA_ERR_SHAPE;
-  hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, R, tiles,
-                     out, out_kind);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return launch_ingest(src, off, hw, B, R, R, out, out_kind, s);
+}
+
+extern "C" int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw,
+                                    void* out, int out_kind, hipStream_t s) {
+  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, s);
 }

@@ -20,21 +20,37 @@ from torch.utils.data._utils.collate import default_collate
 RAW_KEYS = ('image_raw', 'image_off', 'image_hw')
 
 
-def ingest_geometry(w: int, h: int, R: int) -> Tuple[int, int, int, int]:
-    """``(nw, nh, top, left)`` of LargestCenterSquare(R) on a ``w x h`` image: the shorter side is resized to R and the
-    longer one to ``floor(R * long / short)`` (torchvision ``resize`` with an int size), then ``CenterCrop(R)`` takes
-    the window whose origin is ``round((n - R) / 2)``, halves rounded to even (Python ``round``)."""
-    if w < 1 or h < 1 or R < 1:
-        raise ValueError(f'ingest_geometry: w, h, R must be positive, got {(w, h, R)}')
-    new_long = (R * max(w, h)) // min(w, h)
-    nw, nh = (R, new_long) if w <= h else (new_long, R)
+def target_hw(R) -> Tuple[int, int]:
+    """The ingest target as ``(Rh, Rw)`` rows x columns: an int is the square ``(R, R)``, a pair is taken as it is."""
+    if isinstance(R, (tuple, list)) or (hasattr(R, '__len__') and not isinstance(R, str)):
+        if len(R) != 2:
+            raise ValueError(f'an image size is an int or an (Rh, Rw) pair, got {R!r}')
+        return int(R[0]), int(R[1])
+    return int(R), int(R)
 
-    def origin(n):
-        d = n - R
+
+def ingest_geometry(w: int, h: int, R) -> Tuple[int, int, int, int]:
+    """``(nw, nh, top, left)`` of the resize and centre crop of a ``w x h`` image to ``R``, an int or an ``(Rh, Rw)`` pair.
+
+    An int is LargestCenterSquare(R): the shorter side is resized to R and the longer one to ``floor(R * long / short)``
+    (torchvision ``resize`` with an int size).  A pair resizes to cover ``Rh`` rows x ``Rw`` columns the same way: with
+    ``w * Rh <= h * Rw`` the width goes to ``Rw`` and the height to ``floor(Rw * h / w)``, else the height to ``Rh`` and the
+    width to ``floor(Rh * w / h)``; at ``Rh == Rw`` that is the square rule.  Then the centre crop takes the window whose
+    origin per axis is ``round((n - R) / 2)``, halves rounded to even (Python ``round``, torchvision ``CenterCrop``)."""
+    Rh, Rw = target_hw(R)
+    if w < 1 or h < 1 or Rh < 1 or Rw < 1:
+        raise ValueError(f'ingest_geometry: w, h, R must be positive, got {(w, h, R)}')
+    if w * Rh <= h * Rw:
+        nw, nh = Rw, (Rw * h) // w
+    else:
+        nw, nh = (Rh * w) // h, Rh
+
+    def origin(n, r):
+        d = n - r
         q = d // 2
         return q if d % 2 == 0 else q + (q & 1)
 
-    return nw, nh, origin(nh), origin(nw)
+    return nw, nh, origin(nh, Rh), origin(nw, Rw)
 
 
 def decode_rgb(data: bytes) -> np.ndarray:
@@ -87,12 +103,13 @@ def pack_images(images: List[torch.Tensor], pin_memory: bool = False):
 
 class collate_raw_images:
     """Collate function for samples carrying ``image_u8``: packs the images (``pack_images``), default-collates every
-    other key, and records the target side as the Python int ``image_size`` when one was given.  The packed tensor is
-    allocated pinned when ``pin_memory`` is set (and a device is present), so the training step's upload is asynchronous
-    without a second host copy."""
+    other key, and records the target as ``image_size`` when one was given: the Python int it was given, or an
+    ``(Rh, Rw)`` tuple for a rectangular target.  The packed tensor is allocated pinned when ``pin_memory`` is set (and a
+    device is present), so the training step's upload is asynchronous without a second host copy."""
 
-    def __init__(self, image_size: int = 0, pin_memory: bool = False):
-        self.image_size, self.pin_memory = int(image_size), bool(pin_memory)
+    def __init__(self, image_size=0, pin_memory: bool = False):
+        self.image_size = target_hw(image_size) if hasattr(image_size, '__len__') else int(image_size)
+        self.pin_memory = bool(pin_memory)
 
     def __call__(self, samples):
         pin = self.pin_memory and torch.cuda.is_available()
@@ -104,28 +121,36 @@ class collate_raw_images:
         return batch
 
 
-def is_raw_image_directory(directory: str, resize_size: int) -> bool:
-    """An MDS directory whose ``index.json`` lists a ``jpg`` column and no ``latents_{resize_size}`` column."""
+def is_raw_image_directory(directory: str, resize_size) -> bool:
+    """An MDS directory whose ``index.json`` lists a ``jpg`` column and no ``latents_{resize_size}`` column.  Latent columns
+    exist for square sizes only, so for an ``(Rh, Rw)`` pair the ``jpg`` column alone decides."""
     import json
     import os
     with open(os.path.join(directory, 'index.json')) as f:
         shards = json.load(f)['shards']
     names = set().union(*[set(s['column_names']) for s in shards]) if shards else set()
+    if hasattr(resize_size, '__len__'):
+        return 'jpg' in names
     return 'jpg' in names and f'latents_{resize_size}' not in names
 
 
-def ingest_batch(batch, R: int, kind: int, device):
-    """Upload a raw batch (non-blocking) and run the ingest kernel: kind 0 -> bf16 [B*R*R, 8], kind 1 -> fp32 [B,3,R,R]."""
+def ingest_batch(batch, R, kind: int, device):
+    """Upload a raw batch (non-blocking) and run the ingest kernel for the target ``R``, an int or an ``(Rh, Rw)`` pair:
+    kind 0 -> bf16 [B*Rh*Rw, 8], kind 1 -> fp32 [B,3,Rh,Rw].  An int runs the square entry, a pair the rectangular one."""
     from .. import ops
     raw, off, hw = (batch[k] for k in RAW_KEYS)
     if off.is_cuda or hw.is_cuda:
         raise ValueError('ingest_batch: image_off / image_hw must still be host tensors (ingest before moving the batch to '
                          'the device): the bounds of the packed buffer are checked on them')
     B = off.numel()
+    Rh, Rw = target_hw(R)
     d_raw, d_off, d_hw = (z.to(device, non_blocking=True) for z in (raw, off, hw))
     if kind == 0:
-        out = torch.empty(B * R * R, 8, device=device, dtype=torch.bfloat16)
+        out = torch.empty(B * Rh * Rw, 8, device=device, dtype=torch.bfloat16)
     else:
-        out = torch.empty(B, 3, R, R, device=device, dtype=torch.float32)
-    ops.image_ingest(d_raw, d_off, d_hw, R, out, kind, host=(off, hw))
+        out = torch.empty(B, 3, Rh, Rw, device=device, dtype=torch.float32)
+    if isinstance(R, int):
+        ops.image_ingest(d_raw, d_off, d_hw, R, out, kind, host=(off, hw))
+    else:
+        ops.image_ingest_rect(d_raw, d_off, d_hw, Rh, Rw, out, kind, host=(off, hw))
     return out

@@ -12,7 +12,9 @@ here, so two backends exist:
     (N(0,1) latents / text embeddings), which is what bench.py and the tests use.
 JPEG decode (:83) is skipped when latents are present: the reference decodes images it never uses.  A
 ``local`` MDS directory with a ``jpg`` column and no ``latents_{resize_size}`` column is read as raw images instead
-(``datasets/image_ingest.py``): batches then carry ``image_raw`` / ``image_off`` / ``image_hw`` / ``image_size``."""
+(``datasets/image_ingest.py``): batches then carry ``image_raw`` / ``image_off`` / ``image_hw`` / ``image_size``.
+``resize_size`` may be an ``(Rh, Rw)`` pair for such directories (a rectangular target, ``image_size`` is then the tuple);
+latent columns, latent shards and the synthetic data are square, so a pair anywhere else is a ``ValueError``."""
 from __future__ import annotations
 
 import glob
@@ -129,7 +131,7 @@ def build_streaming_laion_dataloader(
     batch_size: int = 1,
     tokenizer_name_or_path: str = 'stabilityai/stable-diffusion-2-base',
     caption_drop_prob: float = 0.0,
-    resize_size: int = 256,
+    resize_size: Union[int, Sequence[int]] = 256,
     num_samples: Optional[int] = None,
     predownload: int = 100_000,
     download_retry: int = 2,
@@ -148,6 +150,14 @@ def build_streaming_laion_dataloader(
     text_dim = dataloader_kwargs.pop('text_dim', 1024)
     with_images = dataloader_kwargs.pop('synthetic_images', False)
     seed = int(dataloader_kwargs.pop('seed', 17))
+    # an (Rh, Rw) pair: a rectangular target, which only the raw-image ingest can produce (latent columns, latent shards and
+    # the synthetic data are square)
+    rect = hasattr(resize_size, '__len__')
+    if rect:
+        from ..image_ingest import target_hw
+        resize_size = target_hw(resize_size)
+        if min(resize_size) < 1:
+            raise ValueError(f'resize_size must be positive, got {resize_size}')
     if local:
         missing = [d for d in local if not os.path.isdir(d)]
         if missing:  # never fall through to synthetic noise because of a mistyped path
@@ -162,6 +172,9 @@ def build_streaming_laion_dataloader(
         if any(raw) and not all(raw):
             raise ValueError('raw-image and latent directories cannot be mixed in one dataloader: '
                              f'{[d for d, r in zip(local, raw) if r]} hold images only')
+        if rect and not all(raw):
+            raise ValueError(f'resize_size={list(resize_size)}: a rectangular size needs raw-image MDS directories (a `jpg` '
+                             f'column); {[d for d, r in zip(local, raw) if not r]} hold latents, which are square')
         if all(raw):
             parts = [MDSImageDataset(d, tok, caption_drop_prob) for d in local]
             dataloader_kwargs.setdefault('collate_fn', collate_raw_images(
@@ -171,6 +184,9 @@ def build_streaming_laion_dataloader(
                      else LocalLatentShards(d, resize_size) for d in local]
         dataset = torch.utils.data.ConcatDataset(parts)
     else:  # both remote and local empty (the shipped YAML): seeded synthetic data of the same shapes
+        if rect:
+            raise ValueError(f'resize_size={list(resize_size)}: the synthetic dataset is square; a rectangular size needs '
+                             'raw-image MDS directories')
         dataset = SyntheticLAIONDataset(image_size=resize_size, caption_drop_prob=caption_drop_prob, text_dim=text_dim,
                                         with_images=with_images, seed=seed)
     if num_samples is not None:

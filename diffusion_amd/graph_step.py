@@ -5,7 +5,7 @@ buffer: ~1,700 kernel launches issued from Python through the C ABI.  At the ref
 (``device_train_microbatch_size: 16``, SD-2-base-256.yaml:87) the kernels are short and the step is bound by the host
 issuing them (368 images/s against 1,390 at microbatch 256).  Every C-ABI entry point is capture-safe (no allocation,
 no host synchronisation, work only on the given stream), so the whole launch sequence of a microbatch is captured ONCE
-per (batch, latent side, dtype, weight) into a hipGraph and replayed: inputs are copied into static buffers, the
+per (batch, latent height and width, dtype, weight) into a hipGraph and replayed: inputs are copied into static buffers, the
 activations of the captured microbatch live in the graph's private memory pool, gradients accumulate into the same
 flat buffer as in eager mode.
 
@@ -29,7 +29,8 @@ class GraphedMicrobatch:
         unet = model.unet
         dev = unet.device_
         self.model = model
-        self.B, _, self.S, _ = latents.shape
+        self.B, _, H, W = latents.shape
+        self.S = (H, W)
         self.weight = float(weight)
         self.lat = torch.empty_like(latents, device=dev)
         self.cond = torch.empty_like(cond, device=dev)
@@ -50,7 +51,7 @@ class GraphedMicrobatch:
         unet.grad.copy_(keep)
         del keep
         # buffers the captured launches point at but that live outside the graph's pool: keep them alive with the graph
-        # (UNetHIP replaces its scratch when the (batch, side) key changes; SPLITK_WS is module state)
+        # (UNetHIP replaces its scratch when the (batch, height, width) key changes; SPLITK_WS is module state)
         self._keep = (unet._scratch, unet._ss, unet._coef, unet._delta, ops.SPLITK_WS, unet._tdesc if hasattr(unet, '_tdesc') else None)
         cb, unet._grad_ready_cb = unet._grad_ready_cb, None   # host-side hooks do not belong in a captured sequence
         try:

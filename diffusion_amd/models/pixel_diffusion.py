@@ -66,9 +66,9 @@ class PixelDiffusion(ComposerModel):
         """The U-Net under the name the trainer, EMA and checkpointing use (``StableDiffusion.unet``)."""
         return self.model
 
-    def unet_input_side(self, batch) -> int:
-        """Side of the U-Net input for the trainer's microbatch sizing: pixels go in as they are (no VAE, no /8)."""
-        return int(batch[self.input_key].shape[-1])
+    def unet_input_side(self, batch):
+        """``(H, W)`` of the U-Net input for the trainer's microbatch sizing: pixels go in as they are (no VAE, no /8)."""
+        return int(batch[self.input_key].shape[-2]), int(batch[self.input_key].shape[-1])
 
     # ------------------------------------------------------------------------------------------
     def _text_states(self, input_ids):
@@ -90,9 +90,8 @@ class PixelDiffusion(ComposerModel):
         dev = unet.device_
         inputs = batch[self.input_key].to(dev)
         conditioning = self._text_states(batch[self.conditioning_key])
-        B, C, S, S2 = inputs.shape
-        if S != S2:
-            raise ValueError('square inputs only')
+        B, C, H, W = inputs.shape
+        unet.check_spatial(H, W)
         if timesteps is None:
             if self.continuous_time:
                 timesteps = self.scheduler.t_max * torch.rand(B, device=dev, generator=generator)
@@ -103,18 +102,18 @@ class PixelDiffusion(ComposerModel):
         x0 = inputs.float().contiguous()
         eps = noise.to(dev).float().contiguous()
         t = timesteps.to(dev, torch.float32 if self.continuous_time else torch.int64).contiguous()
-        xt = torch.empty(B * S * S, 8, device=dev, dtype=torch.bfloat16)
-        target8 = torch.empty(B * S * S, 8, device=dev, dtype=torch.float32)
+        xt = torch.empty(B * H * W, 8, device=dev, dtype=torch.bfloat16)
+        target8 = torch.empty(B * H * W, 8, device=dev, dtype=torch.float32)
         if self.continuous_time:
             ops.add_noise_ex(x0, eps, t, xt, target8, self.prediction_type)
         else:
             sa, sb = self.scheduler.device_tables(dev)
             ops.add_noise_ex(x0, eps, t, xt, target8, self.prediction_type, sa, sb)
         ctx = unet.prepare_ctx(conditioning)
-        pred8 = unet.forward_features(xt, t, ctx, B, S)
-        pred = pred8.view(B, S, S, 8)[..., :C].permute(0, 3, 1, 2)
-        target = target8.view(B, S, S, 8)[..., :C].permute(0, 3, 1, 2)
-        self._pending = (pred8, target8, B * S * S, C)
+        pred8 = unet.forward_features(xt, t, ctx, B, (H, W))
+        pred = pred8.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2)
+        target = target8.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2)
+        self._pending = (pred8, target8, B * H * W, C)
         return pred, target, timesteps
 
     def loss(self, outputs, batch, weight: float = 1.0):
@@ -198,6 +197,7 @@ class PixelDiffusion(ComposerModel):
         rng_generator = torch.Generator(device=device)
         if seed:
             rng_generator = rng_generator.manual_seed(seed)
+        self.model.check_spatial(int(height), int(width))   # pixels go in as they are: multiples of 2 ** (levels - 1)
         do_cfg = guidance_scale > 1.0
         text_embeddings = self._prepare_text_embeddings(prompt, tokenized_prompts, prompt_embeds, num_images_per_prompt)
         batch_size = len(text_embeddings)

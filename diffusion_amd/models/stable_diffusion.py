@@ -140,16 +140,19 @@ class StableDiffusion(ComposerModel):
     def ingest_raw(self, batch):
         """A batch of packed raw images (``image_raw`` / ``image_off`` / ``image_hw`` from
         ``datasets.image_ingest.collate_raw_images``) -> the same batch with the three keys replaced by what the image encoder
-        reads: ``image_nhwc8`` bf16 [B, R, R, 8] for the HIP VAE encoder, else the reference's fp32 ``image`` [B, 3, R, R].
-        One non-blocking upload of the bytes and one kernel (``ops.image_ingest``): the reference's LargestCenterSquare ->
-        ToTensor -> Normalize (laion.py:159-164).  R is the batch's ``image_size`` (the side the dataloader was built
-        with), else ``unet.config.sample_size * 8``."""
-        from ..datasets.image_ingest import RAW_KEYS, ingest_batch
-        R = int(batch.get('image_size') or self.unet.config.sample_size * 8)
+        reads: ``image_nhwc8`` bf16 [B, Rh, Rw, 8] for the HIP VAE encoder, else the reference's fp32 ``image``
+        [B, 3, Rh, Rw].  One non-blocking upload of the bytes and one kernel (``ops.image_ingest``, or
+        ``ops.image_ingest_rect`` for a rectangular target): the reference's LargestCenterSquare -> ToTensor -> Normalize
+        (laion.py:159-164).  The target is the batch's ``image_size`` (what the dataloader was built with: an int, or an
+        ``(Rh, Rw)`` pair), else ``unet.config.sample_size * 8``."""
+        from ..datasets.image_ingest import RAW_KEYS, ingest_batch, target_hw
+        R = batch.get('image_size') or self.unet.config.sample_size * 8
+        R = target_hw(R) if hasattr(R, '__len__') else int(R)
+        Rh, Rw = target_hw(R)
         hip = getattr(self, 'vae_hip', None) is not None
         out = ingest_batch(batch, R, 0 if hip else 1, self.unet.device_)
         rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k != 'image_size'}
-        rest['image_nhwc8' if hip else self.image_key] = out.view(-1, R, R, 8) if hip else out
+        rest['image_nhwc8' if hip else self.image_key] = out.view(-1, Rh, Rw, 8) if hip else out
         return rest
 
     def _encode(self, batch):
@@ -199,7 +202,8 @@ class StableDiffusion(ComposerModel):
         unet: UNetHIP = self.unet
         dev = unet.device_
         latents = latents.to(dev)
-        B, _, S, S2 = latents.shape
+        B, _, H, W = latents.shape
+        unet.check_spatial(H, W)
         if timesteps is None:
             timesteps = torch.randint(0, len(self.noise_scheduler), (B,), device=dev)
         if noise is None:
@@ -208,15 +212,15 @@ class StableDiffusion(ComposerModel):
         eps = noise.to(dev).float().contiguous()
         t = timesteps.to(dev, torch.int64).contiguous()
         sa, sb = self.noise_scheduler.device_tables(dev)
-        xt = torch.empty(B * S * S2, 8, device=dev, dtype=torch.bfloat16)
-        target8 = torch.empty(B * S * S2, 8, device=dev, dtype=torch.float32)
+        xt = torch.empty(B * H * W, 8, device=dev, dtype=torch.bfloat16)
+        target8 = torch.empty(B * H * W, 8, device=dev, dtype=torch.float32)
         v_pred = self.prediction_type == 'v_prediction'
         ops.add_noise(x0, eps, t, sa, sb, xt, target8, v_pred)
         ctx = unet.prepare_ctx(conditioning.to(dev))
-        pred8 = unet.forward_features(xt, t, ctx, B, S)
-        pred = pred8.view(B, S, S2, 8)[..., :4].permute(0, 3, 1, 2)
-        target = target8.view(B, S, S2, 8)[..., :4].permute(0, 3, 1, 2) if v_pred else noise
-        self._pending = (pred8, target8, B * S * S2)
+        pred8 = unet.forward_features(xt, t, ctx, B, (H, W))
+        pred = pred8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2)
+        target = target8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2) if v_pred else noise
+        self._pending = (pred8, target8, B * H * W)
         return pred, target, timesteps
 
     def loss(self, outputs, batch, weight: float = 1.0):
@@ -331,6 +335,9 @@ class StableDiffusion(ComposerModel):
         vae_scale = 8
         height = height or self.unet.config.sample_size * vae_scale
         width = width or self.unet.config.sample_size * vae_scale
+        if height % vae_scale or width % vae_scale:
+            raise ValueError(f'generate: height and width must be multiples of {vae_scale} (the VAE), got {height} x {width}')
+        self.unet.check_spatial(height // vae_scale, width // vae_scale)   # 8 * 2 ** (levels - 1) pixels: 64 for SD-2
         do_cfg = guidance_scale > 1.0
         text_embeddings = self._prepare_text_embeddings(prompt, tokenized_prompts, prompt_embeds, num_images_per_prompt)
         batch_size = len(text_embeddings)

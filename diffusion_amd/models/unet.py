@@ -321,6 +321,15 @@ class UNetOutput(dict):
         return self['sample']
 
 
+def spatial_hw(S) -> Tuple[int, int]:
+    """The spatial extent of a U-Net input as ``(H, W)`` rows x columns: an int is the square ``(S, S)``."""
+    if isinstance(S, (tuple, list, torch.Size)):
+        if len(S) != 2:
+            raise ValueError(f'a spatial size is an int or an (H, W) pair, got {S!r}')
+        return int(S[0]), int(S[1])
+    return int(S), int(S)
+
+
 _DGRAD_FIRST = os.environ.get('DA_DGRAD_FIRST', '0') == '1'
 
 
@@ -492,24 +501,31 @@ class UNetHIP(nn.Module):
     # ------------------------------------------------------------------------------------------
     # scratch
     # ------------------------------------------------------------------------------------------
-    def _ensure_scratch(self, B, S):
-        key = (B, S)
+    def check_spatial(self, H: int, W: int):
+        """The down path halves each extent ``len(block_out_channels) - 1`` times and the up path doubles it back: the skip
+        connections only meet when both extents are multiples of ``2 ** (levels - 1)`` (diffusers fails on the concat in
+        the same case).  Raises before anything is launched."""
+        f = 2 ** (len(self.cfg.block_out_channels) - 1)
+        if H < f or W < f or H % f or W % f:
+            raise ValueError(f'U-Net input {H} x {W}: height and width must be positive multiples of {f} '
+                             f'(2 ** (len(block_out_channels) - 1)), or the skip connections do not meet')
+
+    def _ensure_scratch(self, B, H, W):
+        key = (B, H, W)
         if self._scratch_key == key:
             return
         cfg = self.cfg
         dev = self.device_
         maxc = 2 * max(cfg.block_out_channels)
         need = 0
-        s = S
-        for lvl in range(4):
-            need = max(need, ops.norm_scratch_floats(B, s * s, maxc))
-            s = max(1, s // 2)
+        for lvl in range(len(cfg.block_out_channels)):
+            need = max(need, ops.norm_scratch_floats(B, max(1, H >> lvl) * max(1, W >> lvl), maxc))
         need = max(need, 256 * 8 * max(cfg.block_out_channels) * 2, 256 * self.tproj_total * 2,
                    1024 * max(cfg.block_out_channels) * 2, 4096)
         self._scratch = torch.empty(need, device=dev, dtype=F32)
         self._ss = torch.empty(B * maxc * 2, device=dev, dtype=F32)
         self._coef = torch.empty(B * cfg.norm_num_groups * 2, device=dev, dtype=F32)
-        self._delta = torch.empty(B * max(cfg.attention_head_dim) * S * S, device=dev, dtype=F32)
+        self._delta = torch.empty(B * max(cfg.attention_head_dim) * H * W, device=dev, dtype=F32)
         if ops.SPLITK_WS is None:  # 128 MiB fp32 slabs for split-K of small-M GEMMs (shared by all calls on the stream)
             ops.SPLITK_WS = torch.empty(32 * 1024 * 1024, device=dev, dtype=F32)
         if self.wgrad_stream is not None:
@@ -766,11 +782,12 @@ class UNetHIP(nn.Module):
     # ------------------------------------------------------------------------------------------
     # whole network
     # ------------------------------------------------------------------------------------------
-    def forward_features(self, xt8: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, B: int, S: int, kv=None,
+    def forward_features(self, xt8: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, B: int, S, kv=None,
                          record: bool = True):
-        """xt8: [B*S*S, 8] bf16 NHWC(8) noised inputs; t: [B] int64 (discrete steps) or fp32 (continuous time);
-        ctx: [B*77, ctx_dim] bf16.  Returns pred [B*S*S, 8] fp32 (channels out_channels..7 are zero) and records
-        everything backward needs.
+        """xt8: [B*H*W, 8] bf16 NHWC(8) noised inputs; t: [B] int64 (discrete steps) or fp32 (continuous time);
+        ctx: [B*77, ctx_dim] bf16; ``S``: the spatial extent, an int (square, H = W = S) or an ``(H, W)`` pair (rows x
+        columns, both multiples of ``2 ** (levels - 1)``: ``check_spatial``).  Returns pred [B*H*W, 8] fp32 (channels
+        out_channels..7 are zero) and records everything backward needs.
 
         The sampling form: ``kv`` (``project_context(ctx)``) replaces the 16 cross-attention K/V GEMMs, and with
         ``record=False`` nothing is kept for a backward - no tape, a block's intermediates die with the block and a concat
@@ -806,7 +823,11 @@ class UNetHIP(nn.Module):
         boc = cfg.block_out_channels
         n = len(boc)
         record = self._record
-        self._ensure_scratch(B, S)
+        H, W = spatial_hw(S)
+        self.check_spatial(H, W)
+        if xt8.shape[0] != B * H * W:
+            raise ValueError(f'forward_features: {xt8.shape[0]} input rows for B * H * W = {B} * {H} * {W}')
+        self._ensure_scratch(B, H, W)
         self._ctx = ctx
         tape = [] if record else _NoTape()   # List[Tuple[str, tuple]]
         # ---- timestep embedding MLP + all 22 time_emb_proj in one GEMM
@@ -829,7 +850,7 @@ class UNetHIP(nn.Module):
         del te0, te1, te1s, temb, tembs
 
         # ---- concat buffers of the up path, allocated when their skip half is produced
-        res = [S >> i for i in range(n)]
+        res = [(H >> i, W >> i) for i in range(n)]
         cats: List[torch.Tensor] = []
         cat_cb: List[int] = []
 
@@ -843,43 +864,43 @@ class UNetHIP(nn.Module):
             cat_cb.append(cb)
             return buf[:, cb:]
 
-        h = skip_slot(B * S * S, boc[0])
+        h = skip_slot(B * H * W, boc[0])
         ci = self.M('conv_in.weight')
-        ops.gemm_nt(xt8, ci.w, h, Geom.conv(B, S, S), bias=self.V('conv_in.bias').p)
-        tape.append(('conv_in', (xt8, B, S)))
+        ops.gemm_nt(xt8, ci.w, h, Geom.conv(B, H, W), bias=self.V('conv_in.bias').p)
+        tape.append(('conv_in', (xt8, B, H, W)))
         for i in range(n):
-            r = res[i]
+            rh, rw = res[i]
             for j in range(cfg.layers_per_block):
                 p = f'down_blocks.{i}.resnets.{j}'
                 if i < n - 1:
-                    h, sv = self._resnet_fwd(p, h, B, r, r)
+                    h, sv = self._resnet_fwd(p, h, B, rh, rw)
                     tape.append(('resnet', sv))
-                    h, sv = self._transformer_fwd(f'down_blocks.{i}.attentions.{j}', h, B, r, r,
-                                                  cfg.attention_head_dim[i], out=skip_slot(B * r * r, boc[i]))
+                    h, sv = self._transformer_fwd(f'down_blocks.{i}.attentions.{j}', h, B, rh, rw,
+                                                  cfg.attention_head_dim[i], out=skip_slot(B * rh * rw, boc[i]))
                     tape.append(('transformer', sv))
                 else:
-                    h, sv = self._resnet_fwd(p, h, B, r, r, out=skip_slot(B * r * r, boc[i]))
+                    h, sv = self._resnet_fwd(p, h, B, rh, rw, out=skip_slot(B * rh * rw, boc[i]))
                     tape.append(('resnet', sv))
                 tape.append(('skip', (len(cats) - 1,)))
             if i < n - 1:
                 m = self.M(f'down_blocks.{i}.downsamplers.0.conv.weight')
-                y = skip_slot(B * (r // 2) * (r // 2), boc[i])
-                ops.gemm_nt(h, m.w, y, Geom.down(B, r, r), bias=self.V(f'down_blocks.{i}.downsamplers.0.conv.bias').p)
-                tape.append(('down', (f'down_blocks.{i}.downsamplers.0.conv', h, B, r)))
+                y = skip_slot(B * (rh // 2) * (rw // 2), boc[i])
+                ops.gemm_nt(h, m.w, y, Geom.down(B, rh, rw), bias=self.V(f'down_blocks.{i}.downsamplers.0.conv.bias').p)
+                tape.append(('down', (f'down_blocks.{i}.downsamplers.0.conv', h, B, rh, rw)))
                 tape.append(('skip', (len(cats) - 1,)))
                 h = y
-        r = res[-1]
-        h, sv = self._resnet_fwd('mid_block.resnets.0', h, B, r, r)
+        rh, rw = res[-1]
+        h, sv = self._resnet_fwd('mid_block.resnets.0', h, B, rh, rw)
         tape.append(('resnet', sv))
-        h, sv = self._transformer_fwd('mid_block.attentions.0', h, B, r, r, cfg.attention_head_dim[-1])
+        h, sv = self._transformer_fwd('mid_block.attentions.0', h, B, rh, rw, cfg.attention_head_dim[-1])
         tape.append(('transformer', sv))
         s = len(cats) - 1
-        h, sv = self._resnet_fwd('mid_block.resnets.1', h, B, r, r, out=cats[s][:, :cat_cb[s]])
+        h, sv = self._resnet_fwd('mid_block.resnets.1', h, B, rh, rw, out=cats[s][:, :cat_cb[s]])
         tape.append(('resnet', sv))
         rev_heads = tuple(reversed(cfg.attention_head_dim))
         rev = tuple(reversed(boc))
         for i in range(n):
-            r = res[n - 1 - i]
+            rh, rw = res[n - 1 - i]
             for j in range(cfg.layers_per_block + 1):
                 last = (i == n - 1 and j == cfg.layers_per_block)
                 cat = cats[s]
@@ -890,12 +911,12 @@ class UNetHIP(nn.Module):
                     nxt = cats[s - 1][:, :cat_cb[s - 1]]
                 p = f'up_blocks.{i}.resnets.{j}'
                 if i > 0:
-                    h, sv = self._resnet_fwd(p, cat, B, r, r)
+                    h, sv = self._resnet_fwd(p, cat, B, rh, rw)
                     tape.append(('resnet', sv))
-                    h, sv = self._transformer_fwd(f'up_blocks.{i}.attentions.{j}', h, B, r, r, rev_heads[i], out=nxt)
+                    h, sv = self._transformer_fwd(f'up_blocks.{i}.attentions.{j}', h, B, rh, rw, rev_heads[i], out=nxt)
                     tape.append(('transformer', sv))
                 else:
-                    h, sv = self._resnet_fwd(p, cat, B, r, r, out=nxt)
+                    h, sv = self._resnet_fwd(p, cat, B, rh, rw, out=nxt)
                     tape.append(('resnet', sv))
                 if not record:
                     cats[s] = cat = None   # consumed
@@ -903,21 +924,21 @@ class UNetHIP(nn.Module):
             if i < n - 1:
                 key = f'up_blocks.{i}.upsamplers.0.conv'
                 y = cats[s][:, :cat_cb[s]]
-                ops.gemm_nt(h, self.M(key + '.weight').w, y, Geom.up(B, r, r), bias=self.V(key + '.bias').p)
-                tape.append(('up', (key, h, B, r)))
+                ops.gemm_nt(h, self.M(key + '.weight').w, y, Geom.up(B, rh, rw), bias=self.V(key + '.bias').p)
+                tape.append(('up', (key, h, B, rh, rw)))
                 h = y
-        a, st = self._gn_fwd(h, 'conv_norm_out', B, S * S, cfg.norm_eps, 1)
-        pred = torch.empty(B * S * S, 8, device=self.device_, dtype=F32)
-        ops.gemm_nt(a, self.M('conv_out.weight').w, pred, Geom.conv(B, S, S), bias=self.V('conv_out.bias').p)
+        a, st = self._gn_fwd(h, 'conv_norm_out', B, H * W, cfg.norm_eps, 1)
+        pred = torch.empty(B * H * W, 8, device=self.device_, dtype=F32)
+        ops.gemm_nt(a, self.M('conv_out.weight').w, pred, Geom.conv(B, H, W), bias=self.V('conv_out.bias').p)
         if not record:
             return pred
-        tape.append(('out', (h, a, st, B, S)))
+        tape.append(('out', (h, a, st, B, H, W)))
         self._tape = tape
         self._cats = cats
         return pred
 
     def backward_features(self, dpred: torch.Tensor):
-        """dpred: [B*S*S, 8] bf16 gradient of the loss w.r.t. ``forward_features`` output.  Accumulates into
+        """dpred: [B*H*W, 8] bf16 gradient of the loss w.r.t. ``forward_features`` output.  Accumulates into
         the flat fp32 gradient buffer."""
         tape, self._tape = self._tape, None
         if tape is None:
@@ -941,13 +962,13 @@ class UNetHIP(nn.Module):
             lo = None
             if kind == 'out':
                 lo = off('conv_norm_out.weight')
-                h, a, st, B, S = sv
+                h, a, st, B, H, W = sv
                 m = self.M('conv_out.weight')
-                g3 = Geom.conv(B, S, S)
+                g3 = Geom.conv(B, H, W)
                 self._wgrad(dpred, a, m.gw, g3, dbias=self.V('conv_out.bias').g, scratch=self._scratch)
-                da = self._bf(B * S * S, m.C)
+                da = self._bf(B * H * W, m.C)
                 ops.gemm_nt(dpred, m.wt, da, g3)
-                dh = self._gn_bwd(h, da, None, 'conv_norm_out', st, B, S * S, 1)
+                dh = self._gn_bwd(h, da, None, 'conv_norm_out', st, B, H * W, 1)
             elif kind == 'resnet':
                 dh = self._resnet_bwd(sv, dh)
                 lo = off(sv[0] + '.norm1.weight')
@@ -955,14 +976,14 @@ class UNetHIP(nn.Module):
                 dh = self._transformer_bwd(sv, dh)
                 lo = off(sv[0] + '.norm.weight')
             elif kind == 'up':
-                key, x, B, r = sv
+                key, x, B, rh, rw = sv
                 lo = off(key + '.weight')
                 m = self.M(key + '.weight')
-                self._wgrad(dh, x, m.gw, Geom.up(B, r, r), dbias=self.V(key + '.bias').g, scratch=self._scratch)
-                dup = self._bf(B * 4 * r * r, m.C)
-                ops.gemm_nt(dh, m.wt, dup, Geom.conv(B, 2 * r, 2 * r))
-                dx = self._bf(B * r * r, m.C)
-                ops.upsample2x_bwd(dup, dx, B, r, r, m.C)
+                self._wgrad(dh, x, m.gw, Geom.up(B, rh, rw), dbias=self.V(key + '.bias').g, scratch=self._scratch)
+                dup = self._bf(B * 4 * rh * rw, m.C)
+                ops.gemm_nt(dh, m.wt, dup, Geom.conv(B, 2 * rh, 2 * rw))
+                dx = self._bf(B * rh * rw, m.C)
+                ops.upsample2x_bwd(dup, dx, B, rh, rw, m.C)
                 dh = dx
             elif kind == 'cat':
                 s, cb = sv
@@ -974,18 +995,18 @@ class UNetHIP(nn.Module):
                 ops.add(dh, dskip.pop(s), tot)
                 dh = tot
             elif kind == 'down':
-                key, x, B, r = sv
+                key, x, B, rh, rw = sv
                 lo = off(key + '.weight')
                 m = self.M(key + '.weight')
-                self._wgrad(dh, x, m.gw, Geom.down(B, r, r), dbias=self.V(key + '.bias').g, scratch=self._scratch)
-                dx = self._bf(B * r * r, m.C)
-                ops.gemm_nt(dh, m.wt, dx, Geom.down_dgrad(B, r, r))
+                self._wgrad(dh, x, m.gw, Geom.down(B, rh, rw), dbias=self.V(key + '.bias').g, scratch=self._scratch)
+                dx = self._bf(B * rh * rw, m.C)
+                ops.gemm_nt(dh, m.wt, dx, Geom.down_dgrad(B, rh, rw))
                 dh = dx
             elif kind == 'conv_in':
-                xt8, B, S = sv
+                xt8, B, H, W = sv
                 tot = self._bf(*dh.shape)
                 ops.add(dh, dskip.pop(0), tot)
-                self._wgrad(tot, xt8, self.M('conv_in.weight').gw, Geom.conv(B, S, S),
+                self._wgrad(tot, xt8, self.M('conv_in.weight').gw, Geom.conv(B, H, W),
                                   dbias=self.V('conv_in.bias').g, scratch=self._scratch)
                 lo = off('conv_in.weight')
             else:  # pragma: no cover
@@ -1019,7 +1040,7 @@ class UNetHIP(nn.Module):
     # diffusers-compatible inference call: unet(sample, timestep, encoder_hidden_states)
     # ------------------------------------------------------------------------------------------
     def to_nhwc8(self, x: torch.Tensor) -> torch.Tensor:
-        """[B,C,S,S] (C <= 8) any float dtype -> [B*S*S, 8] bf16 (pure relayout; used for the un-noised inference path)."""
+        """[B,C,H,W] (C <= 8) any float dtype -> [B*H*W, 8] bf16 (pure relayout; used for the un-noised inference path)."""
         B, C, H, W = x.shape
         out = torch.zeros(B * H * W, 8, device=self.device_, dtype=BF16)
         out.view(B, H, W, 8)[..., :C] = x.permute(0, 2, 3, 1)
@@ -1034,8 +1055,7 @@ class UNetHIP(nn.Module):
 
     def forward(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor, **kw):
         B, C, H, W = sample.shape
-        if H != W:
-            raise ValueError('square latents only')
+        self.check_spatial(H, W)
         if C != self.cfg.in_channels:
             raise ValueError(f'sample has {C} channels, the U-Net takes {self.cfg.in_channels}')
         t = torch.as_tensor(timestep, device=self.device_)
@@ -1043,7 +1063,7 @@ class UNetHIP(nn.Module):
             t = t.expand(B)
         # floating timesteps (continuous time: numpy / Python floats, float tensors) stay floats, embedded unrounded
         t = t.to(F32 if t.is_floating_point() else torch.int64).contiguous()
-        pred = self.forward_features(self.to_nhwc8(sample), t, self.prepare_ctx(encoder_hidden_states), B, H)
+        pred = self.forward_features(self.to_nhwc8(sample), t, self.prepare_ctx(encoder_hidden_states), B, (H, W))
         self._tape = None
         out = pred.view(B, H, W, 8)[..., :self.cfg.out_channels].permute(0, 3, 1, 2)
         return UNetOutput(sample=out)

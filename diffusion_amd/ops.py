@@ -524,6 +524,37 @@ def add_noise_ex(x0, eps, t, xt, target, prediction_type='epsilon', sqrt_ac=None
 IMAGE_INGEST_MAX_SIDE = 65535   # da_image_ingest skips larger sides; rejected here
 
 
+def _image_ingest_args(fn, raw, off, hw, Rh, Rw, out, kind, host):
+    """the checks both ingest entries share; returns B"""
+    for z, dt, nm in ((raw, torch.uint8, 'raw uint8'), (off, torch.int64, 'off int64'), (hw, torch.int32, 'hw int32')):
+        if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != dt or not z.is_contiguous():
+            raise ValueError(f'{fn}: {nm} must be a contiguous device tensor')
+    B = int(off.numel())
+    if raw.dim() != 1 or off.dim() != 1 or B < 1 or tuple(hw.shape) != (B, 2):
+        raise ValueError(f'{fn}: raw [nbytes], off [B], hw [B, 2] with B >= 1')
+    if not (1 <= Rh <= 4096 and 1 <= Rw <= 4096):
+        raise ValueError(f'{fn}: target {Rh} x {Rw} outside 1..4096' if Rh != Rw else f'{fn}: R = {Rh} outside 1..4096')
+    if kind not in (0, 1):
+        raise ValueError(f'{fn}: unknown out kind {kind!r} (0: bf16 NHWC-8, 1: fp32 NCHW)')
+    dt, numel, align = ((BF16, B * Rh * Rw * 8, 16), (F32, B * 3 * Rh * Rw, 4))[kind]
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dt or not out.is_contiguous() \
+            or out.numel() != numel or out.data_ptr() % align:
+        raise ValueError(f'{fn}: out must be a contiguous {dt} device tensor of {numel} elements, '
+                         f'{align}-byte aligned (kind {kind})')
+    if host is None:
+        raise ValueError(f'{fn}: host=(off, hw) copies of the tables are required for the bounds check')
+    h_off, h_hw = (torch.as_tensor(z) for z in host)
+    if h_off.is_cuda or h_hw.is_cuda or h_off.numel() != B or tuple(h_hw.shape) != (B, 2):
+        raise ValueError(f'{fn}: host=(off [B], hw [B, 2]) must be host tensors of the same shapes')
+    h_off, h_hw = h_off.to(torch.int64), h_hw.to(torch.int64)
+    if int(h_hw.min()) < 1 or int(h_hw.max()) > IMAGE_INGEST_MAX_SIDE:
+        raise ValueError(f'{fn}: image sides must be in 1..{IMAGE_INGEST_MAX_SIDE}')
+    end = h_off + 3 * h_hw[:, 0] * h_hw[:, 1]
+    if int(h_off.min()) < 0 or int(end.max()) > raw.numel():
+        raise ValueError(f'{fn}: the offset table runs outside the {raw.numel()}-byte buffer')
+    return B
+
+
 def image_ingest(raw, off, hw, R, out, kind, host=None):
     """LargestCenterSquare(R) + ToTensor + Normalize(0.5, 0.5) of packed RGB uint8 images (``da_image_ingest``).
 
@@ -531,33 +562,19 @@ def image_ingest(raw, off, hw, R, out, kind, host=None):
     out: kind 0 bf16 [B*R*R, 8] (NHWC-8, 16-byte aligned), kind 1 fp32 [B, 3, R, R].  ``host = (off, hw)`` are the host
     copies the collate function made of the two tables: sizes and ``off[b] + 3*h*w <= raw.numel()`` are checked on them,
     never by reading the device tables back.  They are required - the kernel trusts the tables."""
-    for z, dt, nm in ((raw, torch.uint8, 'raw uint8'), (off, torch.int64, 'off int64'), (hw, torch.int32, 'hw int32')):
-        if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != dt or not z.is_contiguous():
-            raise ValueError(f'image_ingest: {nm} must be a contiguous device tensor')
-    B, R = int(off.numel()), int(R)
-    if raw.dim() != 1 or off.dim() != 1 or B < 1 or tuple(hw.shape) != (B, 2):
-        raise ValueError('image_ingest: raw [nbytes], off [B], hw [B, 2] with B >= 1')
-    if not 1 <= R <= 4096:
-        raise ValueError(f'image_ingest: R = {R} outside 1..4096')
-    if kind not in (0, 1):
-        raise ValueError(f'image_ingest: unknown out kind {kind!r} (0: bf16 NHWC-8, 1: fp32 NCHW)')
-    dt, numel, align = ((BF16, B * R * R * 8, 16), (F32, B * 3 * R * R, 4))[kind]
-    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dt or not out.is_contiguous() \
-            or out.numel() != numel or out.data_ptr() % align:
-        raise ValueError(f'image_ingest: out must be a contiguous {dt} device tensor of {numel} elements, '
-                         f'{align}-byte aligned (kind {kind})')
-    if host is None:
-        raise ValueError('image_ingest: host=(off, hw) copies of the tables are required for the bounds check')
-    h_off, h_hw = (torch.as_tensor(z) for z in host)
-    if h_off.is_cuda or h_hw.is_cuda or h_off.numel() != B or tuple(h_hw.shape) != (B, 2):
-        raise ValueError('image_ingest: host=(off [B], hw [B, 2]) must be host tensors of the same shapes')
-    h_off, h_hw = h_off.to(torch.int64), h_hw.to(torch.int64)
-    if int(h_hw.min()) < 1 or int(h_hw.max()) > IMAGE_INGEST_MAX_SIDE:
-        raise ValueError(f'image_ingest: image sides must be in 1..{IMAGE_INGEST_MAX_SIDE}')
-    end = h_off + 3 * h_hw[:, 0] * h_hw[:, 1]
-    if int(h_off.min()) < 0 or int(end.max()) > raw.numel():
-        raise ValueError(f'image_ingest: the offset table runs outside the {raw.numel()}-byte buffer')
+    R = int(R)
+    B = _image_ingest_args('image_ingest', raw, off, hw, R, R, out, kind, host)
     _lib.call('da_image_ingest', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, R, out.data_ptr(), int(kind), _stream())
+
+
+def image_ingest_rect(raw, off, hw, Rh, Rw, out, kind, host=None):
+    """``image_ingest`` for a target of ``Rh`` rows x ``Rw`` columns (``da_image_ingest_rect``): resize to cover, then the
+    centre crop (``datasets.image_ingest.ingest_geometry`` with a pair).  out: kind 0 bf16 [B*Rh*Rw, 8], kind 1 fp32
+    [B, 3, Rh, Rw]; everything else as ``image_ingest``, whose bits it gives at ``Rh == Rw``."""
+    Rh, Rw = int(Rh), int(Rw)
+    B = _image_ingest_args('image_ingest_rect', raw, off, hw, Rh, Rw, out, kind, host)
+    _lib.call('da_image_ingest_rect', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, Rh, Rw, out.data_ptr(), int(kind),
+              _stream())
 
 
 CLIP_MAX_PATCH, CLIP_MAX_SIZE = 32, 448   # da_clip_preprocess: one block stages a P x P patch

@@ -41,12 +41,13 @@ def resolve_sampler(sampler: Optional[str]) -> str:
 class GraphedSamplerStep:
     """One captured denoising step for one signature: forward-only walk + ``sampler_step`` over static buffers."""
 
-    def __init__(self, unet, rows: int, B: int, S: int, C: int, cfg: bool, t_dtype, ctx: torch.Tensor, kv: dict):
+    def __init__(self, unet, rows: int, B: int, HW, C: int, cfg: bool, t_dtype, ctx: torch.Tensor, kv: dict):
         dev = unet.device_
-        self.unet, self.rows, self.S, self.C, self.cfg = unet, rows, S, C, cfg
-        npix = B * S * S
+        H, W = HW
+        self.unet, self.rows, self.HW, self.C, self.cfg = unet, rows, (H, W), C, cfg
+        npix = B * H * W
         self.x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
-        self.xt = torch.zeros(rows * S * S, 8, device=dev, dtype=torch.bfloat16)
+        self.xt = torch.zeros(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
         self.t = torch.zeros(rows, device=dev, dtype=t_dtype)
         self.coef = torch.zeros(4, device=dev, dtype=torch.float32)
         self.ctx = ctx.clone()
@@ -65,7 +66,7 @@ class GraphedSamplerStep:
             self._body()
 
     def _body(self):
-        pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.S, kv=self.kv, record=False)
+        pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.HW, kv=self.kv, record=False)
         ops.sampler_step(pred, self.x, self.coef, self.x, self.xt, None, C=self.C, cfg=self.cfg,
                          copies=2 if self.cfg else 1)
 
@@ -106,20 +107,19 @@ class LatentSampler:
     def sample(self, latents: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor] = None, *,
                num_inference_steps: int, guidance_scale: float, graph: bool = False,
                progress_bar: bool = False) -> torch.Tensor:
-        """latents: the initial noise [B, C, H, H] (already scaled by ``init_noise_sigma``); cond / uncond: [B, L, D] text
+        """latents: the initial noise [B, C, H, W] (already scaled by ``init_noise_sigma``); cond / uncond: [B, L, D] text
         states.  Classifier-free guidance runs iff ``guidance_scale > 1.0`` (``uncond`` is then required).  Returns the
-        denoised [B, C, H, H] fp32 (latent models: before the 1 / 0.18215 rescale)."""
+        denoised [B, C, H, W] fp32 (latent models: before the 1 / 0.18215 rescale)."""
         unet, sch = self.unet, self.scheduler
         dev = unet.device_
-        B, C, S, S2 = latents.shape
-        if S != S2:
-            raise ValueError('square latents only')
+        B, C, H, W = latents.shape
+        unet.check_spatial(H, W)
         if C != unet.cfg.in_channels:
             raise ValueError(f'latents have {C} channels, the U-Net takes {unet.cfg.in_channels}')
         cfg = guidance_scale > 1.0
         if cfg and uncond is None:
             raise ValueError('guidance_scale > 1 needs the unconditional text states')
-        rows, npix = (2 * B if cfg else B), B * S * S
+        rows, npix = (2 * B if cfg else B), B * H * W
         sch.set_timesteps(num_inference_steps)
         ts = sch.timesteps
         ts = ts.tolist() if isinstance(ts, torch.Tensor) else [float(t) for t in ts]
@@ -140,14 +140,14 @@ class LatentSampler:
         copies = 2 if cfg else 1
         g = None
         if graph and not stochastic and ops.PROFILE is None:   # the SDE needs a fresh draw per step: eager
-            key = (rows, S, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1])
-            g = self._graph_for(key, rows, B, S, C, cfg, t_dtype, ctx, kv)
+            key = (rows, H, W, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1])
+            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv)
             g.load(ctx, kv)
             x, xt = g.x, g.xt
             x.zero_()
         else:
             x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
-            xt = torch.empty(rows * S * S, 8, device=dev, dtype=torch.bfloat16)
+            xt = torch.empty(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
         # NCHW -> NHWC-8 of the initial noise (and its bf16 copies) by the step kernel itself: 0 x + 0 m + 1 z
         lat = latents.to(dev, torch.float32).contiguous()
         one = torch.tensor([0.0, 0.0, 1.0, 0.0], device=dev)
@@ -156,8 +156,8 @@ class LatentSampler:
             if g is not None:
                 g.step(t_tab[i], coef_tab[i])
                 continue
-            pred = unet.forward_features(xt, t_tab[i], ctx, rows, S, kv=kv, record=False)
+            pred = unet.forward_features(xt, t_tab[i], ctx, rows, (H, W), kv=kv, record=False)
             # the Euler-Maruyama draw: global generator, after the U-Net call, the shape step() draws (randn_like(sample))
-            noise = torch.randn((B, C, S, S), device=dev) if stochastic else None
+            noise = torch.randn((B, C, H, W), device=dev) if stochastic else None
             ops.sampler_step(pred, x, coef_tab[i], x, xt if i + 1 < n else None, noise, C=C, cfg=cfg, copies=copies)
-        return x.view(B, S, S, 8)[..., :C].permute(0, 3, 1, 2).contiguous()
+        return x.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2).contiguous()

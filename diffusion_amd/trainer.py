@@ -215,15 +215,18 @@ class Trainer:
     # ~60 GB for 256 images at 32^2 -> 0.235 GB/image; the count scales with the pixel count)
     ACT_GB_PER_IMAGE_AT_32 = 0.235
 
-    def auto_microbatch(self, n: int, latent_side: int) -> int:
+    def auto_microbatch(self, n: int, latent_side) -> int:
         """Composer's ``device_train_microbatch_size: auto`` shrinks the microbatch until it fits; here it is computed:
         the largest divisor-free chunk of the per-device batch whose saved activations fit the free HBM (with 25 %
-        head-room for workspaces and the allocator), never more than the batch itself."""
-        key = (n, latent_side)
+        head-room for workspaces and the allocator), never more than the batch itself.  ``latent_side``: the U-Net input's
+        side, or its ``(H, W)`` for a rectangular batch."""
+        from .models.unet import spatial_hw
+        lh, lw = spatial_hw(latent_side)
+        key = (n, lh if lh == lw else (lh, lw))   # a square keeps its (n, side) entry
         if key not in self._auto_mb:
             free, _ = torch.cuda.mem_get_info()
             free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()   # cached blocks are reusable
-            per_image = self.ACT_GB_PER_IMAGE_AT_32 * (latent_side / 32.0)**2 * 2**30
+            per_image = self.ACT_GB_PER_IMAGE_AT_32 * (lh * lw / 1024.0) * 2**30
             cap = max(1, int(0.75 * free / per_image))
             mb = n
             if cap < n:
@@ -231,7 +234,7 @@ class Trainer:
                 mb = -(-n // parts)      # equal-sized microbatches
             self._auto_mb[key] = mb
             if self.rank == 0 and mb != n:
-                print(f'device_train_microbatch_size=auto -> {mb} (batch {n}, latents {latent_side}x{latent_side}, '
+                print(f'device_train_microbatch_size=auto -> {mb} (batch {n}, latents {lh}x{lw}, '
                       f'{free / 2**30:.0f} GiB free)', flush=True)
         return self._auto_mb[key]
 
@@ -252,9 +255,10 @@ class Trainer:
                 side = model.unet_input_side(batch)
             else:
                 lat = batch.get(model.image_latents_key) if model.precomputed_latents else batch.get(model.image_key)
-                side = 32 if lat is None else (lat.shape[-1] if model.precomputed_latents else lat.shape[-1] // 8)
-                if lat is None and not model.precomputed_latents and 'image_nhwc8' in batch:   # ingested raw images [B,R,R,8]
-                    side = batch['image_nhwc8'].shape[1] // 8
+                f = 1 if model.precomputed_latents else 8
+                side = 32 if lat is None else (lat.shape[-2] // f, lat.shape[-1] // f)
+                if lat is None and not model.precomputed_latents and 'image_nhwc8' in batch:   # ingested raw images [B,Rh,Rw,8]
+                    side = (batch['image_nhwc8'].shape[1] // 8, batch['image_nhwc8'].shape[2] // 8)
             mb = self.auto_microbatch(n, side)
         starts = list(range(0, n, mb))
         # the first backward of the step WRITES the flat gradient (no zero fill, no read half of the read-add-writes); a

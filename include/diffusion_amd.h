@@ -291,6 +291,15 @@ int da_sampler_step(const float* pred, const float* x, const float* noise, const
  * DA_ERR_SHAPE for B < 1, R outside 1..4096, an unknown out_kind or a misaligned out. */
 int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out, int out_kind,
                     da_stream_t stream);
+/* The da_image_ingest contract for a rectangular target of Rh rows x Rw columns: resize to cover, then centre crop.  With
+ * w*Rh <= h*Rw the width is resized to Rw and the height to floor(Rw*h/w), else the height to Rh and the width to
+ * floor(Rh*w/h), so the resized image is never smaller than the target on either axis; the crop origin per axis is
+ * round((n - R)/2), halves rounded to even.  Same filter, arithmetic and argument rules.
+ * out_kind 0: bf16 [B*Rh*Rw][8] NHWC, 16-byte aligned; out_kind 1: fp32 [B][3][Rh][Rw].  At Rh == Rw == R every bit of
+ * either output is da_image_ingest's.  DA_ERR_SHAPE for B < 1, Rh or Rw outside 1..4096, an unknown out_kind or a
+ * misaligned out. */
+int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
+                         int out_kind, da_stream_t stream);
 
 /* F.mse_loss(pred, target) (stable_diffusion.py:187) over the 4 valid channels of NHWC(8) fp32 tensors and its
  * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats;
