@@ -21,6 +21,22 @@
 // factor is the larger one lands exactly on its target extent (w Rh <= h Rw: nw = Rw, nh = floor(Rw h / w); else nh = Rh,
 // nw = floor(Rh w / h)), so nw >= Rw and nh >= Rh and the centre crop lies inside the resized image.  At Rh == Rw the test
 // is w <= h and the rule is LargestCenterSquare's: da_image_ingest is the same kernel with Rh = Rw = R.
+//
+// da_image_resize: the same kernel with three independent switches (the COCO evaluation loader's transforms).
+// geometry 1 stretches instead: nw = Rw, nh = Rh, crop origin 0, each axis resized on its own.  range 1 writes v / 255
+// (ToTensor alone) instead of v / 127.5 - 1.  filter 1 is the two-tap bilinear of F.interpolate(align_corners=False,
+// antialias=False): with num = max((2 i + 1) n_in - n_out, 0), i0 = num / (2 n_out) and r = num - 2 n_out i0 the taps are
+// i0 and min(i0 + 1, n_in - 1) with the integer weights 2 n_out - r and r.  That is the window [i0, i0 + 2) clipped at n_in
+// with W = 2 n_out - |num'|, num' starting at -r and stepping by 2 n_out: the antialiased filter's tap loop with M = n_out,
+// so both passes and the normalisation by the integer weight sum are shared.
+//
+// Row walk with filter 1.  The two source rows of an output row are n_in / n_out apart from the next row's, so when
+// reducing the windows of a tile's 16 rows are islands in [vlo, vhi) and not one contiguous run.  Before a chunk is staged
+// every thread finds (from the row table in LDS, the same answer in all threads) the first output row whose window ends
+// after the chunk's start; if that window begins past the chunk, the chunk start jumps forward by whole chunks to the one
+// the window begins in.  A chunk no row falls into is neither read nor filtered, and at most 2 * 16 chunks are staged per
+// tile whatever the reduction.  With filter 0 consecutive windows always touch, so nothing is ever skipped and the walk is
+// the one above.
 #include "common.hpp"
 #include "diffusion_amd.h"
 
@@ -50,11 +66,26 @@ DEVINL void axis_setup(int n_in, int n_out, int i, int* lo_, int* hi_, int* num_
   *inv_ = sum > 0 ? 1.0 / (double)sum : 0.0;
 }
 
+// the two taps of output index i for filter 1, in axis_setup's terms (see the header comment)
+DEVINL void axis_setup_two_tap(int n_in, int n_out, int i, int* lo_, int* hi_, int* num_, double* inv_) {
+  const long long d = 2LL * n_out;
+  long long num = (2LL * i + 1) * n_in - n_out;
+  if (num < 0) num = 0;
+  const long long i0 = num / d;   // <= n_in - 1
+  const int r = (int)(num - i0 * d);
+  const bool two = i0 + 1 < n_in;   // at the last sample both taps are i0: one tap of weight 2 n_out - r, normalised to 1
+  *lo_ = (int)i0;
+  *hi_ = (int)i0 + (two ? 2 : 1);
+  *num_ = -r;
+  *inv_ = 1.0 / (double)(two ? d : d - r);
+}
+
 __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const unsigned char* __restrict__ src,
                                                                           const long long* __restrict__ off,
                                                                           const int* __restrict__ hw, int Rh, int Rw,
                                                                           int tiles_y, int tiles_x,
-                                                                          void* __restrict__ out, int kind) {
+                                                                          void* __restrict__ out, int kind, int geometry,
+                                                                          int filter, int range) {
   __shared__ int s_lo[2][IMG_TILE], s_hi[2][IMG_TILE], s_num[2][IMG_TILE];
   __shared__ double s_inv[2][IMG_TILE];
   __shared__ float s_row[IMG_TILE][IMG_TILE][3];
@@ -64,15 +95,19 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
   const int h = hw[2 * b], w = hw[2 * b + 1];
   if (h < 1 || w < 1 || h > IMG_MAX_SIDE || w > IMG_MAX_SIDE) return;   // uniform over the block, before any barrier
   // geometry: resize to cover Rh x Rw (the tighter axis lands on its target, the other one is floored); crop origin rounded
-  // half to even.  w * Rh, h * Rw <= 65535 * 4096 < 2^31.
+  // half to even.  w * Rh, h * Rw <= 65535 * 4096 < 2^31.  geometry 1 (stretch): the target itself, no crop.
   const bool fit_w = w * Rh <= h * Rw;
-  const int nw = fit_w ? Rw : (int)((long long)Rh * w / h), nh = fit_w ? (int)((long long)Rw * h / w) : Rh;
+  const int nw = geometry || fit_w ? Rw : (int)((long long)Rh * w / h);
+  const int nh = geometry ? Rh : fit_w ? (int)((long long)Rw * h / w) : Rh;
   const int qy = (nh - Rh) >> 1, qx = (nw - Rw) >> 1;
   const int top = ((nh - Rh) & 1) ? qy + (qy & 1) : qy, left = ((nw - Rw) & 1) ? qx + (qx & 1) : qx;
   if (t < 2 * IMG_TILE) {
     const int a = t >> 4, j = t & (IMG_TILE - 1);   // a = 0: columns, 1: rows; indices past the target repeat the last one
     const int i = a ? min(ty0 + j, Rh - 1) + top : min(tx0 + j, Rw - 1) + left;
-    axis_setup(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
+    if (filter)
+      axis_setup_two_tap(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
+    else
+      axis_setup(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
   }
   __syncthreads();
   const unsigned char* img = src + off[b];
@@ -80,10 +115,17 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
   const int xlo = s_lo[0][x], xhi = s_hi[0][x], xnum = s_num[0][x];
   const int ylo = s_lo[1][y], yhi = s_hi[1][y], ynum = s_num[1][y];
   const double xinv = s_inv[0][x];
-  const int M2x = 2 * (w > nw ? w : nw), M2y = 2 * (h > nh ? h : nh);
+  const int M2x = 2 * (!filter && w > nw ? w : nw), M2y = 2 * (!filter && h > nh ? h : nh);
   const int vlo = s_lo[1][0], vhi = s_hi[1][IMG_TILE - 1];   // lo and hi do not decrease with the row
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
   for (int v0 = vlo; v0 < vhi; v0 += IMG_TILE) {
+    if (filter) {   // two-tap windows are islands: jump to the chunk the next window begins in (uniform over the block)
+      int j = 0;
+      while (j < IMG_TILE && s_hi[1][j] <= v0) ++j;
+      if (j == IMG_TILE) break;
+      const int nlo = s_lo[1][j];
+      if (nlo >= v0 + IMG_TILE) v0 += (nlo - v0) / IMG_TILE * IMG_TILE;
+    }
     const int v = v0 + y;   // horizontal pass: this thread's source row of the chunk, output column x
     if (v < vhi) {
       const unsigned char* p = img + ((long)v * w + xlo) * 3;
@@ -114,8 +156,9 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
   }
   const int Y = ty0 + y, X = tx0 + x;
   if (Y >= Rh || X >= Rw) return;
-  const double k = s_inv[1][y] * (1.0 / 127.5);   // ToTensor (/255) and Normalize(0.5, 0.5): v / 127.5 - 1
-  const float o0 = (float)(acc0 * k - 1.0), o1 = (float)(acc1 * k - 1.0), o2 = (float)(acc2 * k - 1.0);
+  // range 0: ToTensor (/255) and Normalize(0.5, 0.5), v / 127.5 - 1; range 1: ToTensor alone, v / 255
+  const double k = s_inv[1][y] * (range ? 1.0 / 255.0 : 1.0 / 127.5), sub = range ? 0.0 : 1.0;
+  const float o0 = (float)(acc0 * k - sub), o1 = (float)(acc1 * k - sub), o2 = (float)(acc2 * k - sub);
   if (kind == 0) {
     bf16x8 o = zero8();
     o[0] = f2bf(o0);
@@ -131,8 +174,9 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
 }
 
 int launch_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
-                  int out_kind, hipStream_t s) {
+                  int out_kind, int geometry, int filter, int range, hipStream_t s) {
   DA_CLEAR_ERR();
+  if ((geometry | filter | range) & ~1) return DA_ERR_SHAPE;
   if (B < 1 || Rh < 1 || Rh > 4096 || Rw < 1 || Rw > 4096 || (out_kind != 0 && out_kind != 1) || !src || !off || !hw ||
       !out)
     return DA_ERR_SHAPE;
@@ -142,7 +186,7 @@ int launch_ingest(const unsigned char* src, const long long* off, const int* hw,
   const long blocks = (long)B * tiles_y * tiles_x;
   if (blocks > 0x7fffffffL) return DA_ERR_SHAPE;
   hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, Rh, Rw,
-                     tiles_y, tiles_x, out, out_kind);
+                     tiles_y, tiles_x, out, out_kind, geometry, filter, range);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -151,10 +195,15 @@ int launch_ingest(const unsigned char* src, const long long* off, const int* hw,
 
 extern "C" int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out,
                                int out_kind, hipStream_t s) {
-  return launch_ingest(src, off, hw, B, R, R, out, out_kind, s);
+  return launch_ingest(src, off, hw, B, R, R, out, out_kind, 0, 0, 0, s);
 }
 
 extern "C" int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw,
                                     void* out, int out_kind, hipStream_t s) {
-  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, s);
+  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, 0, 0, 0, s);
+}
+
+extern "C" int da_image_resize(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw,
+                               void* out, int out_kind, int geometry, int filter, int range, hipStream_t s) {
+  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, geometry, filter, range, s);
 }

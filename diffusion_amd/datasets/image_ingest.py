@@ -18,6 +18,7 @@ from torch.utils.data import Dataset
 from torch.utils.data._utils.collate import default_collate
 
 RAW_KEYS = ('image_raw', 'image_off', 'image_hw')
+TRANSFORM_KEYS = ('geometry', 'filter', 'range')   # batch['image_transform']: the ops.image_resize switches
 
 
 def target_hw(R) -> Tuple[int, int]:
@@ -105,11 +106,14 @@ class collate_raw_images:
     """Collate function for samples carrying ``image_u8``: packs the images (``pack_images``), default-collates every
     other key, and records the target as ``image_size`` when one was given: the Python int it was given, or an
     ``(Rh, Rw)`` tuple for a rectangular target.  The packed tensor is allocated pinned when ``pin_memory`` is set (and a
-    device is present), so the training step's upload is asynchronous without a second host copy."""
+    device is present), so the training step's upload is asynchronous without a second host copy.  ``image_transform``
+    (the COCO evaluation loader's) rides along as ``batch['image_transform']``: a dict of the ``ops.image_resize`` switches
+    ``geometry`` / ``filter`` / ``range``; without one the key is absent and the batch means the training transform."""
 
-    def __init__(self, image_size=0, pin_memory: bool = False):
+    def __init__(self, image_size=0, pin_memory: bool = False, image_transform=None):
         self.image_size = target_hw(image_size) if hasattr(image_size, '__len__') else int(image_size)
         self.pin_memory = bool(pin_memory)
+        self.image_transform = None if image_transform is None else {k: int(image_transform[k]) for k in TRANSFORM_KEYS}
 
     def __call__(self, samples):
         pin = self.pin_memory and torch.cuda.is_available()
@@ -118,6 +122,8 @@ class collate_raw_images:
         batch['image_raw'], batch['image_off'], batch['image_hw'] = raw, off, hw
         if self.image_size:
             batch['image_size'] = self.image_size
+        if self.image_transform is not None:
+            batch['image_transform'] = dict(self.image_transform)
         return batch
 
 
@@ -134,9 +140,10 @@ def is_raw_image_directory(directory: str, resize_size) -> bool:
     return 'jpg' in names and f'latents_{resize_size}' not in names
 
 
-def ingest_batch(batch, R, kind: int, device):
+def ingest_batch(batch, R, kind: int, device, transform=None):
     """Upload a raw batch (non-blocking) and run the ingest kernel for the target ``R``, an int or an ``(Rh, Rw)`` pair:
-    kind 0 -> bf16 [B*Rh*Rw, 8], kind 1 -> fp32 [B,3,Rh,Rw].  An int runs the square entry, a pair the rectangular one."""
+    kind 0 -> bf16 [B*Rh*Rw, 8], kind 1 -> fp32 [B,3,Rh,Rw].  An int runs the square entry, a pair the rectangular one;
+    with a ``transform`` (a batch's ``image_transform``) ``ops.image_resize`` runs with its switches instead."""
     from .. import ops
     raw, off, hw = (batch[k] for k in RAW_KEYS)
     if off.is_cuda or hw.is_cuda:
@@ -149,7 +156,9 @@ def ingest_batch(batch, R, kind: int, device):
         out = torch.empty(B * Rh * Rw, 8, device=device, dtype=torch.bfloat16)
     else:
         out = torch.empty(B, 3, Rh, Rw, device=device, dtype=torch.float32)
-    if isinstance(R, int):
+    if transform is not None:
+        ops.image_resize(d_raw, d_off, d_hw, Rh, Rw, out, kind, *(int(transform[k]) for k in TRANSFORM_KEYS), host=(off, hw))
+    elif isinstance(R, int):
         ops.image_ingest(d_raw, d_off, d_hw, R, out, kind, host=(off, hw))
     else:
         ops.image_ingest_rect(d_raw, d_off, d_hw, Rh, Rw, out, kind, host=(off, hw))

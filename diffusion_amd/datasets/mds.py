@@ -11,7 +11,10 @@ version 2, no compression - the reference writes ``compression=None``, precomput
                          sample blobs
   sample blob          : uint32 size for every variable-size column (in column order) | column payloads in order
   column order         : the writer sorts the columns by NAME; readers must follow index.json's ``column_names``
-  encodings used here  : bytes, str (utf-8), int8..int64 / uint8..uint64 / float16..float64 (numpy scalars), int (int64)
+  encodings used here  : bytes, str (utf-8), int8..int64 / uint8..uint64 / float16..float64 (numpy scalars), int (int64),
+                         json (a UTF-8 JSON document), jpeg / png (the encoded file's bytes, handed on undecoded) and pil
+                         (a raw PIL image, decoded to an RGB array: ``_decode_pil``) - what a COCO directory uses
+                         (scripts/convert_coco.py:55 writes {'image': 'jpeg', 'captions': 'json'})
 No file produced by the real package is available offline; besides the round trip through ``write_mds`` the reader is
 tested on a shard assembled byte by byte from this layout with ``struct`` (tests/test_abi_and_host.py), including the
 config blob, name-sorted columns and the b'' latents of images below the resolution."""
@@ -32,9 +35,34 @@ def _fixed_size(enc: str) -> Optional[int]:
     return _SCALARS[enc].itemsize if enc in _SCALARS else None
 
 
+def _decode_pil(raw: bytes) -> np.ndarray:
+    """streaming's ``pil`` encoding -> ``uint8 [h, w, 3]`` RGB.  The layout is restated FROM MEMORY of the published package
+    (no file it wrote is available here): three uint32 ``width, height, len(mode)``, the mode string, then the image's raw
+    ``tobytes()`` payload.  Non-RGB modes are converted."""
+    from PIL import Image
+    width, height, n = (int(v) for v in np.frombuffer(raw[:12], np.uint32))
+    mode = raw[12:12 + n].decode('utf-8')
+    img = Image.frombytes(mode, (width, height), raw[12 + n:])
+    if img.mode != 'RGB':
+        img = img.convert('RGB')
+    return np.array(img, dtype=np.uint8)
+
+
+def _encode_pil(value) -> bytes:
+    """a PIL image (or a uint8 array Pillow can wrap) in the layout ``_decode_pil`` reads"""
+    from PIL import Image
+    img = value if isinstance(value, Image.Image) else Image.fromarray(np.asarray(value))
+    mode = img.mode.encode('utf-8')
+    return np.array([img.width, img.height, len(mode)], np.uint32).tobytes() + mode + img.tobytes()
+
+
 def _decode(enc: str, raw: bytes):
-    if enc == 'bytes' or enc in ('jpeg', 'png', 'pil'):
+    if enc == 'bytes' or enc in ('jpeg', 'png'):
         return raw
+    if enc == 'pil':
+        return _decode_pil(raw)
+    if enc == 'json':
+        return json.loads(raw.decode('utf-8'))
     if enc == 'str':
         return raw.decode('utf-8')
     if enc in _SCALARS:
@@ -43,8 +71,12 @@ def _decode(enc: str, raw: bytes):
 
 
 def _encode(enc: str, value) -> bytes:
-    if enc == 'bytes':
+    if enc == 'bytes' or enc in ('jpeg', 'png'):   # jpeg / png: the ready-encoded file
         return bytes(value)
+    if enc == 'pil':
+        return _encode_pil(value)
+    if enc == 'json':
+        return json.dumps(value).encode('utf-8')
     if enc == 'str':
         return str(value).encode('utf-8')
     if enc in _SCALARS:

@@ -144,14 +144,20 @@ class StableDiffusion(ComposerModel):
         [B, 3, Rh, Rw].  One non-blocking upload of the bytes and one kernel (``ops.image_ingest``, or
         ``ops.image_ingest_rect`` for a rectangular target): the reference's LargestCenterSquare -> ToTensor -> Normalize
         (laion.py:159-164).  The target is the batch's ``image_size`` (what the dataloader was built with: an int, or an
-        ``(Rh, Rw)`` pair), else ``unet.config.sample_size * 8``."""
+        ``(Rh, Rw)`` pair), else ``unet.config.sample_size * 8``.
+
+        A batch with an ``image_transform`` (the COCO evaluation loader's: the ``ops.image_resize`` switches) always becomes
+        the fp32 ``image`` [B, 3, Rh, Rw] in [0, 1], HIP VAE or not: ``eval_forward`` reads its size to generate at and
+        ``update_metric`` hands it to the image metrics.  The VAE then sees un-normalised [0, 1] images at evaluation, as in
+        the reference (coco_captions.py:105-108 has no Normalize)."""
         from ..datasets.image_ingest import RAW_KEYS, ingest_batch, target_hw
         R = batch.get('image_size') or self.unet.config.sample_size * 8
         R = target_hw(R) if hasattr(R, '__len__') else int(R)
         Rh, Rw = target_hw(R)
-        hip = getattr(self, 'vae_hip', None) is not None
-        out = ingest_batch(batch, R, 0 if hip else 1, self.unet.device_)
-        rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k != 'image_size'}
+        transform = batch.get('image_transform')
+        hip = getattr(self, 'vae_hip', None) is not None and transform is None
+        out = ingest_batch(batch, R, 0 if hip else 1, self.unet.device_, transform)
+        rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k not in ('image_size', 'image_transform')}
         rest['image_nhwc8' if hip else self.image_key] = out.view(-1, Rh, Rw, 8) if hip else out
         return rest
 

@@ -525,7 +525,7 @@ IMAGE_INGEST_MAX_SIDE = 65535   # da_image_ingest skips larger sides; rejected h
 
 
 def _image_ingest_args(fn, raw, off, hw, Rh, Rw, out, kind, host):
-    """the checks both ingest entries share; returns B"""
+    """the checks the ingest entries share; returns B"""
     for z, dt, nm in ((raw, torch.uint8, 'raw uint8'), (off, torch.int64, 'off int64'), (hw, torch.int32, 'hw int32')):
         if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != dt or not z.is_contiguous():
             raise ValueError(f'{fn}: {nm} must be a contiguous device tensor')
@@ -575,6 +575,21 @@ def image_ingest_rect(raw, off, hw, Rh, Rw, out, kind, host=None):
     B = _image_ingest_args('image_ingest_rect', raw, off, hw, Rh, Rw, out, kind, host)
     _lib.call('da_image_ingest_rect', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, Rh, Rw, out.data_ptr(), int(kind),
               _stream())
+
+
+def image_resize(raw, off, hw, Rh, Rw, out, kind, geometry, filter, range, host=None):
+    """``image_ingest_rect`` with the transform as three switches (``da_image_resize``, the same kernel): ``geometry`` 0
+    resize to cover + centre crop, 1 stretch each axis on its own; ``filter`` 0 the antialiased triangle filter (Pillow,
+    ``F.interpolate(antialias=True)``), 1 two-tap bilinear (``F.interpolate(align_corners=False, antialias=False)``);
+    ``range`` 0 ``v / 127.5 - 1``, 1 ``v / 255``.  ``(0, 0, 0)`` gives ``image_ingest_rect``'s bits.  Arguments, outputs and
+    the host-side bounds check are ``image_ingest_rect``'s."""
+    Rh, Rw = int(Rh), int(Rw)
+    B = _image_ingest_args('image_resize', raw, off, hw, Rh, Rw, out, kind, host)
+    for nm, val in (('geometry', geometry), ('filter', filter), ('range', range)):
+        if val not in (0, 1):
+            raise ValueError(f'image_resize: {nm} must be 0 or 1, got {val!r}')
+    _lib.call('da_image_resize', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), B, Rh, Rw, out.data_ptr(), int(kind),
+              int(geometry), int(filter), int(range), _stream())
 
 
 CLIP_MAX_PATCH, CLIP_MAX_SIZE = 32, 448   # da_clip_preprocess: one block stages a P x P patch

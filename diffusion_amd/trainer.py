@@ -56,6 +56,10 @@ class Callback:
     def fit_end(self, trainer):
         pass
 
+    def eval_batch_end(self, trainer, batch, outputs, index):
+        """after the metric updates of evaluation batch ``index`` (0-based) of a ``Trainer.eval()``; ``batch`` is on the device"""
+        pass
+
 
 class SpeedMonitor(Callback):
     """samples/sec over a sliding window of batches (composer.callbacks.SpeedMonitor, window_size=10 in the YAML)."""
@@ -376,7 +380,9 @@ class Trainer:
         logged as ``metrics/eval/<name>``.  A ``CLIPScore`` among the validation metrics (metrics/clip_score.py) is fed the
         images ``eval_forward`` generates per entry of ``val_guidance_scales`` and reduces its own two-float state over the
         ranks in ``compute()``; FID / Inception score need a network whose op set is not on the HIP path and stay out of
-        scope.  With no eval dataloader this returns {}."""
+        scope.  Callbacks get ``eval_batch_end`` after each batch's metric updates.  Nothing collective runs before the final
+        reduction, so the ranks may see different numbers of batches (the COCO loader's unpadded partition).  With no eval
+        dataloader this returns {}."""
         if self.eval_dataloader is None:
             return {}
         model = self.model
@@ -394,6 +400,8 @@ class Trainer:
             outputs = model.eval_forward(batch)
             for m in metrics.values():
                 model.update_metric(batch, outputs, m)
+            for c in self.callbacks:
+                c.eval_batch_end(self, batch, outputs, i)
         out = {}
         for name, m in metrics.items():
             if self.world > 1 and getattr(m, 'sum_squared_error', None) is not None:

@@ -300,6 +300,19 @@ int da_image_ingest(const unsigned char* src, const long long* off, const int* h
  * misaligned out. */
 int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
                          int out_kind, da_stream_t stream);
+/* The same kernel with the transform as three independent switches (every combination is valid); src, off, hw, out and
+ * out_kind are da_image_ingest_rect's, and da_image_ingest_rect is this entry with (0, 0, 0).
+ *   geometry 0: resize to cover Rh x Rw, then the centre crop;  1: stretch, each axis resized on its own to Rw and Rh;
+ *   filter   0: the antialiased triangle filter (Pillow's; F.interpolate(mode='bilinear', antialias=True));
+ *            1: two-tap bilinear, F.interpolate(mode='bilinear', align_corners=False, antialias=False): for output index
+ *               i of an n_in -> n_out axis num = max((2i+1) n_in - n_out, 0), i0 = num / (2 n_out), r = num - 2 n_out i0,
+ *               weights (2 n_out - r) / (2 n_out) on i0 and r / (2 n_out) on min(i0 + 1, n_in - 1);
+ *   range    0: v / 127.5 - 1 (ToTensor + Normalize(0.5, 0.5));  1: v / 255 (ToTensor alone): a constant image of level c
+ *               comes out as exactly float(c) / float(255).
+ * Weights are exact integers and the sums run in fp64 for both filters.  DA_ERR_SHAPE (nothing launched) for any other
+ * value of geometry, filter or range, and for everything da_image_ingest_rect rejects. */
+int da_image_resize(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
+                    int out_kind, int geometry, int filter, int range, da_stream_t stream);
 
 /* F.mse_loss(pred, target) (stable_diffusion.py:187) over the 4 valid channels of NHWC(8) fp32 tensors and its
  * gradient dpred = grad_coef * (pred - target) (bf16, NHWC(8)).  loss[0] (+)= weight * mean.  scratch >= 1024 floats;

@@ -12,6 +12,13 @@ For ``--images`` seeded ``width x height`` RGB sources and R = 256 and 512:
                   do), median of 5
   upload_fp32_ms  the fp32 [B,3,R,R] batch to the device (pinned source), median of 5; ``upload_u8_ms`` the packed bytes
   vae_encode_ms   ``VAEEncoderHIP.moments_nhwc8`` on the ingested batch (random-init full-size VAE), median of 3
+
+  python tools/ingest_bench.py --geometry {0,1} --filter {0,1} [--images 64] [--width 640] [--height 480] [--repeats 20]
+
+With ``--geometry`` / ``--filter`` (one given: the other is 0) the other forms of the kernel are timed instead
+(``ops.image_resize``, range 1, kind 1: the COCO evaluation loader's transforms) against the same transform in torch ops on
+the device - ``uint8 -> fp32 / 255 -> F.interpolate(mode='bilinear', align_corners=False, antialias=filter == 0)`` to the
+resized extent, then the crop - both by device events, plus the largest difference between the two results.
 """
 import argparse
 import json
@@ -45,6 +52,57 @@ def _window(n_in, n_out, first, last):
     return lo, hi
 
 
+def resize_forms(a):
+    """--geometry / --filter: ops.image_resize against F.interpolate on the device"""
+    import torch
+    import torch.nn.functional as F
+    from diffusion_amd import ops
+    from diffusion_amd.datasets.image_ingest import ingest_geometry, pack_images
+    if not torch.cuda.is_available():
+        raise SystemExit('ingest_bench: no GPU')
+    dev = torch.device('cuda:0')
+    B, w, h, g, f = a.images, a.width, a.height, a.geometry or 0, a.filter or 0
+    rng = np.random.default_rng(17)
+    base = rng.integers(0, 256, (B, h // 8 + 1, w // 8 + 1, 3), dtype=np.uint8).repeat(8, 1).repeat(8, 2)[:, :h, :w]
+    imgs = (base.astype(np.int16) + rng.integers(-20, 21, (B, h, w, 3), dtype=np.int16)).clip(0, 255).astype(np.uint8)
+    raw, off, hw = pack_images([torch.from_numpy(im) for im in imgs])
+    d_raw, d_off, d_hw = raw.to(dev), off.to(dev), hw.to(dev)
+    d_u8 = torch.from_numpy(imgs).to(dev)
+
+    def timed(fn, reps, warm=3):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), min(ms), max(ms)
+
+    res = {'bench': 'image_resize', 'images': B, 'source': [w, h], 'repeats': a.repeats, 'geometry': g, 'filter': f,
+           'range': 1, 'shapes': []}
+    for R in (256, 512):
+        nw, nh, top, left = (R, R, 0, 0) if g else ingest_geometry(w, h, R)
+        out = torch.empty(B, 3, R, R, device=dev)
+
+        def torch_path():
+            x = d_u8.permute(0, 3, 1, 2).float() / 255
+            x = F.interpolate(x, size=(nh, nw), mode='bilinear', align_corners=False, antialias=f == 0)
+            return x[:, :, top:top + R, left:left + R].contiguous()
+
+        med, lo, hi = timed(lambda: ops.image_resize(d_raw, d_off, d_hw, R, R, out, 1, g, f, 1, host=(off, hw)), a.repeats)
+        t_med, t_lo, t_hi = timed(torch_path, a.repeats)
+        diff = float((out - torch_path()).abs().max())
+        res['shapes'].append({'R': R, 'kernel_ms': round(med, 4), 'min_ms': round(lo, 4), 'max_ms': round(hi, 4),
+                              'torch_ms': round(t_med, 4), 'torch_min_ms': round(t_lo, 4), 'torch_max_ms': round(t_hi, 4),
+                              'max_abs_diff_vs_torch': diff})
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
@@ -53,7 +111,11 @@ def main():
     ap.add_argument('--repeats', type=int, default=20)
     ap.add_argument('--workers', type=int, default=16)
     ap.add_argument('--no-vae', action='store_true')
+    ap.add_argument('--geometry', type=int, choices=(0, 1), default=None, help='0 cover + centre crop, 1 stretch')
+    ap.add_argument('--filter', type=int, choices=(0, 1), default=None, help='0 antialiased triangle, 1 two-tap bilinear')
     a = ap.parse_args()
+    if a.geometry is not None or a.filter is not None:
+        return resize_forms(a)
     B, w, h = a.images, a.width, a.height
     rng = np.random.default_rng(17)
     # smooth seeded content plus noise, so that neither the filter nor a cache sees a constant
