@@ -59,6 +59,63 @@ __global__ void sampler_step_kernel(const float* pred, const float* x, const flo
   }
 }
 
+// The two-step (DPM-Solver++ 2M) form of the same launch: one operand wider.  The host reduces a step to five coefficients
+// (DPMSolverMultistepScheduler.step_coefficients_ms) and the kernel carries the previous step's data prediction in `hist`:
+//   m     = cfg ? pu + g (pt - pu) : p
+//   d     = ax x + am m                         the data prediction x0 of this step
+//   v     = kx x + k0 d (+ k1 hist)             k1 == 0 (a first-order step): hist is not read, it may hold anything
+//   hist  = d,  x_out = v,  xt = bf16(v)        channels C..7 of all three exactly 0
+// k1 comes from device memory like the rest, so one captured launch serves first- and second-order steps alike.
+// every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
+__global__ void sampler_step_ms_kernel(const float* pred, const float* x, float* hist, const float* coef, float* x_out,
+                                       bf16* xt_out, long npix, int C, int cfg, int copies) {
+  const f32x4 ka = *reinterpret_cast<const f32x4*>(coef), kb = *reinterpret_cast<const f32x4*>(coef + 4);
+  const float ax = ka[0], am = ka[1], kx = ka[2], k0 = ka[3], k1 = kb[0], g = kb[1];
+  const bool second = k1 != 0.0f;  // uniform across the launch
+  GRID_STRIDE(i, npix) {
+    const f32x4 x0 = *reinterpret_cast<const f32x4*>(x + i * 8), x1 = *reinterpret_cast<const f32x4*>(x + i * 8 + 4);
+    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
+    f32x4 q0 = p0, q1 = p1;
+    if (cfg) {  // uniform: rows [npix, 2 npix) are the conditional half
+      q0 = *reinterpret_cast<const f32x4*>(pred + (npix + i) * 8);
+      q1 = *reinterpret_cast<const f32x4*>(pred + (npix + i) * 8 + 4);
+    }
+    f32x4 h0 = {0, 0, 0, 0}, h1 = {0, 0, 0, 0};
+    if (second) {
+      h0 = *reinterpret_cast<const f32x4*>(hist + i * 8);
+      h1 = *reinterpret_cast<const f32x4*>(hist + i * 8 + 4);
+    }
+    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        const float xv = c < 4 ? x0[c & 3] : x1[c & 3], pu = c < 4 ? p0[c & 3] : p1[c & 3];
+        float m = pu;
+        if (cfg) {
+          const float pt = c < 4 ? q0[c & 3] : q1[c & 3];
+          m = pu + g * (pt - pu);
+        }
+        const float dv = ax * xv + am * m;
+        float v = kx * xv + k0 * dv;
+        if (second) v += k1 * (c < 4 ? h0[c & 3] : h1[c & 3]);
+        d[c] = dv;
+        o[c] = v;
+      }
+    }
+    *reinterpret_cast<f32x4*>(hist + i * 8) = f32x4{d[0], d[1], d[2], d[3]};
+    *reinterpret_cast<f32x4*>(hist + i * 8 + 4) = f32x4{d[4], d[5], d[6], d[7]};
+    *reinterpret_cast<f32x4*>(x_out + i * 8) = f32x4{o[0], o[1], o[2], o[3]};
+    *reinterpret_cast<f32x4*>(x_out + i * 8 + 4) = f32x4{o[4], o[5], o[6], o[7]};
+    if (xt_out) {
+      bf16x8 t;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) t[c] = f2bf(o[c]);
+      st8(xt_out + i * 8, t);
+      if (copies == 2) st8(xt_out + (npix + i) * 8, t);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out,
@@ -72,6 +129,21 @@ extern "C" int da_sampler_step(const float* pred, const float* x, const float* n
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef, x_out,
                      (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_sampler_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out,
+                                  void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return DA_ERR_SHAPE;
+  if (!pred || !x || !hist || !coef || !x_out) return DA_ERR_SHAPE;
+  if ((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)hist | (uintptr_t)coef | (uintptr_t)x_out | (uintptr_t)xt_out) & 15))
+    return DA_ERR_SHAPE;
+  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(sampler_step_ms_kernel, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef, x_out,
+                     (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

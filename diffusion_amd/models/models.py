@@ -24,7 +24,8 @@ import torch
 from .composer_shim import MeanSquaredError
 from ..schedulers.schedulers import ContinuousTimeScheduler
 from .pixel_diffusion import PixelDiffusion
-from .schedulers import DDIMScheduler, DDPMScheduler
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
+                         check_inference_scheduler, make_inference_scheduler)
 from .stable_diffusion import StableDiffusion
 from .unet import UNetConfig, UNetHIP
 
@@ -86,7 +87,11 @@ def stable_diffusion_2(
     build_encoders: Optional[bool] = None,
     unet_config: Optional[UNetConfig] = None,
     seed: int = 17,
+    inference_scheduler: str = 'ddim',
 ):
+    """``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's)
+    or ``'dpm++2m'`` (``DPMSolverMultistepScheduler``)."""
+    check_inference_scheduler(inference_scheduler)
     if train_metrics is None:
         train_metrics = [MeanSquaredError()]
     if val_metrics is None:
@@ -154,7 +159,7 @@ def stable_diffusion_2(
             text_hip = TextEncoderHIP(text_encoder)
         text_encoder = text_encoder.to(dtype)
     noise_scheduler = DDPMScheduler(prediction_type=unet_config.prediction_type)
-    inference_noise_scheduler = DDIMScheduler(prediction_type=unet_config.prediction_type)
+    inference_noise_scheduler = make_inference_scheduler(inference_scheduler, prediction_type=unet_config.prediction_type)
 
     model = StableDiffusion(
         unet=unet,
@@ -201,17 +206,19 @@ def _pixel_unet(unet_config: Optional[UNetConfig], seed: int) -> UNetHIP:
 
 
 def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
-                             unet_config: Optional[UNetConfig] = None, seed: int = 17):
-    """Discrete-time (DDPM, 1000 steps) pixel diffusion; DDIM for inference (reference models.py:115-172)."""
+                             unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler: str = 'ddim'):
+    """Discrete-time (DDPM, 1000 steps) pixel diffusion; DDIM for inference (reference models.py:115-172), or with
+    ``inference_scheduler='dpm++2m'`` the second-order multistep solver (``DPMSolverMultistepScheduler``)."""
+    check_inference_scheduler(inference_scheduler)
     if not torch.cuda.is_available():
         raise RuntimeError('discrete_pixel_diffusion: an MI355X is required (the U-Net has no CPU path)')
     unet = _pixel_unet(unet_config, seed)
     text_encoder, tokenizer, text_hip = _pixel_text_encoder(clip_model_name, unet.cfg.cross_attention_dim)
     noise_scheduler = DDPMScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
                                     beta_schedule='scaled_linear', prediction_type=prediction_type, clip_sample=False)
-    inference_scheduler = DDIMScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
-                                        beta_schedule='scaled_linear', clip_sample=False, steps_offset=1,
-                                        prediction_type=prediction_type)
+    inference_scheduler = make_inference_scheduler(inference_scheduler, num_train_timesteps=1000, beta_start=0.00085,
+                                                   beta_end=0.012, beta_schedule='scaled_linear', clip_sample=False,
+                                                   steps_offset=1, prediction_type=prediction_type)
     model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
                            prediction_type=prediction_type, train_metrics=[MeanSquaredError()],
                            val_metrics=[MeanSquaredError()])
@@ -221,10 +228,14 @@ def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch
 
 def continuous_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
                                use_ode=False, train_t_max=1.570795, inference_t_max=1.56,
-                               unet_config: Optional[UNetConfig] = None, seed: int = 17):
+                               unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler=None):
     """Continuous-time pixel diffusion: the VP process with angle = time (tangent schedule), t in [0, train_t_max) for
     training, the reverse SDE (or with ``use_ode`` the probability-flow ODE) from ``inference_t_max`` for generation
-    (reference models.py:175-228)."""
+    (reference models.py:175-228).  ``inference_scheduler`` exists to refuse: the named solvers (``'ddim'``,
+    ``'dpm++2m'``) and multistep scheduler objects are discrete-time methods and raise ``ValueError``."""
+    check_inference_scheduler(inference_scheduler, continuous_time=True)
+    if inference_scheduler is not None:
+        raise ValueError('continuous_pixel_diffusion builds its own ContinuousTimeScheduler (use_ode, inference_t_max)')
     if not torch.cuda.is_available():
         raise RuntimeError('continuous_pixel_diffusion: an MI355X is required (the U-Net has no CPU path)')
     unet = _pixel_unet(unet_config, seed)

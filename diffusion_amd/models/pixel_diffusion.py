@@ -20,6 +20,7 @@ import torch
 from .. import ops
 from ..sampling import LatentSampler, resolve_sampler
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
+from .schedulers import check_inference_scheduler, resolve_inference_scheduler
 from .stable_diffusion import _HIPBackward, _check_prompt_given, _check_prompt_lenths, tqdm
 from .unet import UNetHIP
 
@@ -183,15 +184,21 @@ class PixelDiffusion(ComposerModel):
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None, height: int = 64, width: int = 64,
                  num_inference_steps: Optional[int] = 50, guidance_scale: Optional[float] = 3.0,
                  num_images_per_prompt: Optional[int] = 1, seed: Optional[int] = None,
-                 progress_bar: Optional[bool] = True, sampler: Optional[str] = None):
+                 progress_bar: Optional[bool] = True, sampler: Optional[str] = None, inference_scheduler=None):
         """Reverse diffusion from noise with classifier-free guidance on the HIP U-Net forward (reference :137-241).
         Returns images in [0, 1], (batch * num_images_per_prompt, 3, h, w).
 
         ``sampler``: ``'hip'`` (``sampling.LatentSampler``: forward-only walk, context K/V projected once, one fused
         guidance + scheduler-step launch per step), ``'graph'`` (the same, one hipGraph replay per step; the SDE runs
         eagerly) or ``'torch'`` (the reference's loop, the scheduler step in torch ops); default ``DA_SAMPLER``, else
-        ``'hip'``."""
+        ``'hip'``.
+
+        ``inference_scheduler``: the solver of this call only: ``'ddim'``, ``'dpm++2m'`` (``DPMSolverMultistepScheduler``
+        on the model's noise tables) or a scheduler object; default the model's own.  Discrete-time models only: a
+        continuous-time model raises ``ValueError`` for a name or a multistep scheduler."""
         sampler = resolve_sampler(sampler)
+        check_inference_scheduler(inference_scheduler)   # before `self` is read
+        scheduler = resolve_inference_scheduler(inference_scheduler, self.inference_scheduler, self.continuous_time)
         _check_prompt_given(prompt, tokenized_prompts, prompt_embeds)
         device = self.model.device_
         rng_generator = torch.Generator(device=device)
@@ -211,21 +218,21 @@ class PixelDiffusion(ComposerModel):
                 text_embeddings = torch.cat([uncond, text_embeddings])
         images = torch.randn((batch_size, self.model.config.in_channels, height, width), device=device,
                              generator=rng_generator)
-        self.inference_scheduler.set_timesteps(num_inference_steps)
-        images = images * self.inference_scheduler.init_noise_sigma
+        scheduler.set_timesteps(num_inference_steps)
+        images = images * scheduler.init_noise_sigma
         if sampler != 'torch':
-            images = LatentSampler(self.model, self.inference_scheduler).sample(
+            images = LatentSampler(self.model, scheduler).sample(
                 images, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
                 guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar)
         else:   # the reference's loop, the scheduler step in torch ops
-            for t in tqdm(self.inference_scheduler.timesteps, disable=not progress_bar):
+            for t in tqdm(scheduler.timesteps, disable=not progress_bar):
                 model_input = torch.cat([images] * 2) if do_cfg else images
-                model_input = self.inference_scheduler.scale_model_input(model_input, t)
+                model_input = scheduler.scale_model_input(model_input, t)
                 model_output = self.model(model_input, t, encoder_hidden_states=text_embeddings).sample
                 if do_cfg:   # only technically correct for epsilon prediction (reference :226)
                     pred_uncond, pred_text = model_output.chunk(2)
                     model_output = pred_uncond + guidance_scale * (pred_text - pred_uncond)
-                images = self.inference_scheduler.step(model_output, t, images, generator=rng_generator)['prev_sample']
+                images = scheduler.step(model_output, t, images, generator=rng_generator)['prev_sample']
         images = (images / 2 + 0.5).clamp(0, 1)
         return images.detach().float()
 

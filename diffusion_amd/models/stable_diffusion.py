@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..sampling import LatentSampler, resolve_sampler
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
+from .schedulers import check_inference_scheduler, resolve_inference_scheduler
 from .unet import UNetHIP
 from .vae import DiagonalGaussian
 
@@ -323,13 +324,17 @@ class StableDiffusion(ComposerModel):
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None, height: Optional[int] = None,
                  width: Optional[int] = None, num_inference_steps: int = 50, guidance_scale: float = 3.0,
                  num_images_per_prompt: int = 1, seed: Optional[int] = None, progress_bar: bool = True,
-                 sampler: Optional[str] = None):
+                 sampler: Optional[str] = None, inference_scheduler=None):
         """DDIM sampling with classifier-free guidance on the HIP U-Net forward (reference :260-382).
 
         ``sampler``: ``'hip'`` (``sampling.LatentSampler``: forward-only walk, context K/V projected once, one fused
         guidance + scheduler-step launch per step), ``'graph'`` (the same, one hipGraph replay per step) or ``'torch'``
-        (the reference's loop in torch ops around ``unet(...)``); default ``DA_SAMPLER``, else ``'hip'``."""
+        (the reference's loop in torch ops around ``unet(...)``); default ``DA_SAMPLER``, else ``'hip'``.
+
+        ``inference_scheduler``: the solver of this call only: ``'ddim'``, ``'dpm++2m'`` (``DPMSolverMultistepScheduler``
+        on the model's noise tables) or a scheduler object; default the model's own (``self.inference_scheduler``)."""
         sampler = resolve_sampler(sampler)
+        check_inference_scheduler(inference_scheduler)
         _check_prompt_given(prompt, tokenized_prompts, prompt_embeds)
         _check_prompt_lenths(prompt, negative_prompt)
         _check_prompt_lenths(tokenized_prompts, tokenized_negative_prompts)
@@ -356,21 +361,22 @@ class StableDiffusion(ComposerModel):
                 text_embeddings = torch.cat([uncond, text_embeddings])
         latents = torch.randn((batch_size, self.unet.config.in_channels, height // vae_scale, width // vae_scale),
                               device=device, generator=rng)
-        self.inference_scheduler.set_timesteps(num_inference_steps)
-        latents = latents * self.inference_scheduler.init_noise_sigma
+        scheduler = resolve_inference_scheduler(inference_scheduler, self.inference_scheduler)
+        scheduler.set_timesteps(num_inference_steps)
+        latents = latents * scheduler.init_noise_sigma
         if sampler != 'torch':
-            latents = LatentSampler(self.unet, self.inference_scheduler).sample(
+            latents = LatentSampler(self.unet, scheduler).sample(
                 latents, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
                 guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar)
         else:   # the reference's loop, the scheduler step in torch ops
-            for t in tqdm(self.inference_scheduler.timesteps, disable=not progress_bar):
+            for t in tqdm(scheduler.timesteps, disable=not progress_bar):
                 lin = torch.cat([latents] * 2) if do_cfg else latents
-                lin = self.inference_scheduler.scale_model_input(lin, t)
+                lin = scheduler.scale_model_input(lin, t)
                 pred = self.unet(lin, t, encoder_hidden_states=text_embeddings).sample
                 if do_cfg:
                     pu, pt = pred.chunk(2)
                     pred = pu + guidance_scale * (pt - pu)
-                latents = self.inference_scheduler.step(pred, t, latents, generator=rng)['prev_sample']
+                latents = scheduler.step(pred, t, latents, generator=rng)['prev_sample']
         latents = 1 / 0.18215 * latents
         # image decoder: the HIP-kernel walk of the same frozen weights when the factory built one (models/vae_hip.py),
         # else the PyTorch-ROCm module

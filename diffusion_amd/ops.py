@@ -676,6 +676,33 @@ def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copie
               copies, _stream())
 
 
+def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1):
+    """One sampling step of a two-step scheduler after the U-Net call (``da_sampler_step_ms``): guidance, the data
+    prediction, the update with the previous step's data prediction and the next U-Net input.  ``coef`` = {ax, am, kx, k0,
+    k1, guidance, 0, 0} on the device (``DPMSolverMultistepScheduler.step_coefficients_ms``).
+
+    pred fp32 [(2 if cfg else 1) * npix, 8]; x / x_out / hist fp32 [npix, 8] (x_out may be x; hist is read iff k1 != 0 and
+    then overwritten with this step's data prediction); xt_out None or bf16 [copies * npix, 8]."""
+    C, copies, cfg = int(C), int(copies), bool(cfg)
+    if not 1 <= C <= 8 or copies not in (1, 2):
+        raise ValueError(f'sampler_step_ms: C = {C} (1..8), copies = {copies} (1 or 2)')
+    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
+        raise ValueError('sampler_step_ms: x must be [npix, 8]')
+    npix = x.shape[0]
+    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (hist, npix, 'hist'), (x_out, npix, 'x_out')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
+            raise ValueError(f'sampler_step_ms: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
+    if hist.data_ptr() in (x.data_ptr(), x_out.data_ptr(), pred.data_ptr()):
+        raise ValueError('sampler_step_ms: hist must be a buffer of its own')
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
+        raise ValueError('sampler_step_ms: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
+    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
+                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
+        raise ValueError(f'sampler_step_ms: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    _lib.call('da_sampler_step_ms', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(), x_out.data_ptr(),
+              xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
+
+
 def add_noise(x0, eps, t, sqrt_ac, sqrt_1mac, xt, target, v_pred):
     B = x0.shape[0]
     HW = x0.shape[2] * x0.shape[3]

@@ -278,6 +278,17 @@ int da_add_noise_ex(const float* x0, const float* eps, const void* t, int t_is_f
  * npix <= 0 or no multiple of HW, a NULL pred / x / coef / x_out, or a pointer that is not 16-byte aligned. */
 int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, void* xt_out,
                     long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+/* The same step for a two-step scheduler (DPMSolverMultistepScheduler, DPM-Solver++ 2M): one operand wider, the previous
+ * step's data prediction.  pred / x / x_out / xt_out / npix / C / cfg / copies as in da_sampler_step; there is no noise draw.
+ *   hist   fp32 [npix][8], read (second-order steps only) and then overwritten in place with this step's data prediction;
+ *   coef   DEVICE pointer to eight floats {ax, am, kx, k0, k1, guidance, 0, 0} (step_coefficients_ms of the scheduler).
+ * Per pixel and channel c < C, in fp32 and in this order: m = cfg ? pu + g (pt - pu) : p; x0 = ax x + am m;
+ * v = kx x + k0 x0; if k1 != 0: v += k1 hist; then hist = x0, x_out = v, xt = bf16(v).  With k1 == 0 (a first-order step)
+ * hist is not read at all: it may hold anything, NaN included.  Channels C..7 of x_out, hist and xt_out are exactly 0
+ * whatever the inputs hold there.  Every load of a pixel precedes its first store: x_out may be x.  DA_ERR_SHAPE as for
+ * da_sampler_step, and for a NULL or misaligned hist. */
+int da_sampler_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out, void* xt_out,
+                       long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
 
 /* LargestCenterSquare(R) + ToTensor + Normalize(0.5,0.5) of B packed RGB uint8 images (transforms.py:9-21, laion.py:159-164):
  * PIL's antialiased bilinear resize of the shorter side to R (the longer one to floor(R*long/short)), the centre crop with

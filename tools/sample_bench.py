@@ -3,6 +3,7 @@ step in torch ops), ``'hip'`` (``sampling.LatentSampler``) and ``'graph'`` (the 
 one JSON line.
 
   python tools/sample_bench.py [--batches 1,4,16] [--steps 20] [--px 256] [--guidance 3.0] [--seconds 6] [--model NAME]
+                                [--scheduler ddim|dpm++2m]
 
 SD-2-base U-Net, random init, precomputed text embeddings (no VAE, no text encoder: the loop alone), latents of
 ``px / 8``.  Per batch size B (2 B U-Net rows with guidance):
@@ -13,6 +14,9 @@ SD-2-base U-Net, random init, precomputed text embeddings (no VAE, no text encod
     host clock around each call closed by a device synchronise, until ``--seconds`` have been spent on the batch size;
   * ``ms_per_step`` and ``images_per_s`` are from the median call; ``spread`` is (max - min) / median over the calls;
   * ``rel_l2_vs_torch`` compares the final latents of the same seeded inputs.
+``--scheduler dpm++2m`` runs the three modes with ``DPMSolverMultistepScheduler`` and adds a fourth to the same rounds,
+``ddim_hip`` (the ``'hip'`` mode with the DDIM scheduler), so that the per-step times of the two solvers come from
+interleaved calls of one session.
 """
 import argparse
 import json
@@ -36,17 +40,22 @@ def main():
     ap.add_argument('--guidance', type=float, default=3.0)
     ap.add_argument('--seconds', type=float, default=6.0)
     ap.add_argument('--model', default='stabilityai/stable-diffusion-2-base')
+    ap.add_argument('--scheduler', default='ddim', choices=('ddim', 'dpm++2m'))
     a = ap.parse_args()
 
     import torch
     from diffusion_amd.models.models import stable_diffusion_2
+    from diffusion_amd.models.schedulers import make_inference_scheduler
     from diffusion_amd.sampling import LatentSampler
     if not torch.cuda.is_available():
         raise SystemExit('sample_bench: no GPU')
     dev = torch.device('cuda:0')
-    model = stable_diffusion_2(model_name=a.model, pretrained=False, precomputed_latents=True, fsdp=False)
+    model = stable_diffusion_2(model_name=a.model, pretrained=False, precomputed_latents=True, fsdp=False,
+                               inference_scheduler=a.scheduler)
     unet, sch = model.unet, model.inference_scheduler
     sampler = LatentSampler(unet, sch)
+    modes = MODES + (('ddim_hip',) if a.scheduler != 'ddim' else ())
+    ddim_sampler = LatentSampler(unet, make_inference_scheduler('ddim', like=sch))
     S, D = a.px // 8, unet.cfg.cross_attention_dim
     cfg = a.guidance > 1.0
 
@@ -66,18 +75,20 @@ def main():
     def run(mode, lat, txt, unc):
         if mode == 'torch':
             return torch_loop(lat, txt, unc)
+        if mode == 'ddim_hip':
+            return ddim_sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance)
         return sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance, graph=mode == 'graph')
 
-    res = {'bench': 'sample', 'model': a.model, 'px': a.px, 'steps': a.steps, 'guidance': a.guidance,
+    res = {'bench': 'sample', 'model': a.model, 'scheduler': a.scheduler, 'px': a.px, 'steps': a.steps, 'guidance': a.guidance,
            'seconds_per_batch': a.seconds, 'batches': []}
     for B in (int(b) for b in a.batches.split(',')):
         g = torch.Generator().manual_seed(100 + B)
         lat = torch.randn(B, unet.cfg.in_channels, S, S, generator=g).to(dev)
         txt, unc = torch.randn(B, 77, D, generator=g).to(dev), torch.randn(B, 77, D, generator=g).to(dev)
-        row, outs, times = {'B': B}, {}, {m: [] for m in MODES}
+        row, outs, times = {'B': B}, {}, {m: [] for m in modes}
         sampler.graphs.clear()
         run('hip', lat, txt, unc)   # scratch and workspaces of this shape exist before any peak is read
-        for m in MODES:
+        for m in modes:
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             torch.cuda.reset_peak_memory_stats()
@@ -88,8 +99,8 @@ def main():
             row[m] = {'peak_mib': round(peak / 2**20, 1), 'above_resident_mib': round((peak - base) / 2**20, 1)}
         t_end, rnd = time.perf_counter() + a.seconds, 0
         while time.perf_counter() < t_end or rnd < 3:
-            for k in range(len(MODES)):
-                m = MODES[(k + rnd) % len(MODES)]
+            for k in range(len(modes)):
+                m = modes[(k + rnd) % len(modes)]
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 run(m, lat, txt, unc)
@@ -97,11 +108,15 @@ def main():
                 times[m].append(time.perf_counter() - t0)
             rnd += 1
         ref = outs['torch'].float()
-        for m in MODES:
+        for m in modes:
             med = statistics.median(times[m])
             row[m].update(ms_per_step=round(med * 1e3 / a.steps, 3), images_per_s=round(B / med, 2), calls=len(times[m]),
-                          spread=round((max(times[m]) - min(times[m])) / med, 3),
-                          rel_l2_vs_torch=float(f'{((outs[m].float() - ref).norm() / ref.norm()).item():.3e}'))
+                          spread=round((max(times[m]) - min(times[m])) / med, 3))
+            if m in MODES:   # ddim_hip is another solver: its latents are not comparable
+                row[m]['rel_l2_vs_torch'] = float(f'{((outs[m].float() - ref).norm() / ref.norm()).item():.3e}')
+        if 'ddim_hip' in modes:
+            row['hip']['ms_per_step_vs_ddim_hip'] = round(statistics.median(times['hip']) /
+                                                          statistics.median(times['ddim_hip']), 4)
         for m in ('hip', 'graph'):
             row[m]['speedup_vs_torch'] = round(statistics.median(times['torch']) / statistics.median(times[m]), 3)
         res['batches'].append(row)
