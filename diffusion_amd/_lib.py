@@ -68,6 +68,9 @@ SIGNATURES = {
     'da_clip_score': [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _vp],
     'da_sampler_step': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_ms': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_step_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_step_ms_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_init': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     'da_mse_loss': [_fp, _fp, _vp, _fp, _fp, _l, _f, _f, _i, _vp],
     'da_mse_loss_c': [_fp, _fp, _vp, _fp, _fp, _l, _i, _f, _f, _i, _vp],
     'da_adamw': [_fp, _fp, _fp, _fp, _vp, _fp, _f, _l, _f, _f, _f, _f, _f, _i, _f, _vp],

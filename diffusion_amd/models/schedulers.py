@@ -51,6 +51,13 @@ class DDPMScheduler:
         a, s = self._coef(timesteps, sample)
         return a * noise - s * sample
 
+    def add_noise_coefficients(self, timestep):
+        """``add_noise`` at one timestep as two Python floats (a, s), computed in float64 from the fp32 ``alphas_cumprod``
+        table: noisy = a * original + s * noise.  What ``ops.sampler_init`` and the blended sampler steps apply on the
+        device to start a sample from an image and to re-noise its kept part."""
+        ac = float(self.alphas_cumprod[int(timestep)])
+        return math.sqrt(ac), math.sqrt(1.0 - ac)
+
 
 class DDIMScheduler(DDPMScheduler):
     """eta = 0 DDIM sampler, ``set_alpha_to_one=False``, ``steps_offset=1`` (SD-2 scheduler_config.json)."""
@@ -147,6 +154,13 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
     def _reset(self):
         self._step_index, self._prev_x0, self._prev_lambda = 0, None, None
 
+    def set_begin_index(self, i: int):
+        """The stateful ``step()`` starts at step ``i`` of the schedule (image-to-image: only the tail is run) with no
+        history, so its first step is first order and ``lower_order_final`` still finds the last one.  ``set_timesteps``
+        resets it to 0."""
+        self._reset()
+        self._step_index = int(i)
+
     def set_timesteps(self, num_inference_steps: int, device=None):
         self.num_inference_steps = num_inference_steps
         ratio = self.num_train_timesteps // num_inference_steps
@@ -177,10 +191,11 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
         n = self.num_inference_steps
         return self.solver_order == 2 and i > 0 and not (self.lower_order_final and n < 15 and i == n - 1)
 
-    def step_coefficients_ms(self, i: int):
+    def step_coefficients_ms(self, i: int, first: bool = False):
         """Step number ``i`` of the current schedule as five Python floats (ax, am, kx, k0, k1), computed in float64:
         x0 = ax * sample + am * model_output, prev_sample = kx * sample + k0 * x0 + k1 * (the x0 of step i - 1); k1 is
-        exactly 0.0 on a first-order step.  ``prediction_type``, the order switches and the schedule are read now."""
+        exactly 0.0 on a first-order step.  ``prediction_type``, the order switches and the schedule are read now.
+        ``first``: the step is the first one executed (a schedule entered at ``i`` > 0 has no history): first order."""
         i = int(i)
         stride = self.num_train_timesteps // self.num_inference_steps
         t = int(self.timesteps[i])
@@ -189,7 +204,7 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
         ax, am = self._data_prediction(a_s, s_s)
         h = l_t - l_s
         kd = -a_t * math.expm1(-h)
-        if not self._second_order(i):
+        if first or not self._second_order(i):
             return ax, am, s_t / s_s, kd, 0.0
         r = (l_s - self._alpha_sigma_lambda(int(self.timesteps[i - 1]))[2]) / h
         return ax, am, s_t / s_s, kd * (1.0 + 0.5 / r), -kd * (0.5 / r)

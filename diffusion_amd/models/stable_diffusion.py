@@ -324,7 +324,8 @@ class StableDiffusion(ComposerModel):
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None, height: Optional[int] = None,
                  width: Optional[int] = None, num_inference_steps: int = 50, guidance_scale: float = 3.0,
                  num_images_per_prompt: int = 1, seed: Optional[int] = None, progress_bar: bool = True,
-                 sampler: Optional[str] = None, inference_scheduler=None):
+                 sampler: Optional[str] = None, inference_scheduler=None, init_image: Optional[torch.Tensor] = None,
+                 strength: float = 0.8, mask: Optional[torch.Tensor] = None):
         """DDIM sampling with classifier-free guidance on the HIP U-Net forward (reference :260-382).
 
         ``sampler``: ``'hip'`` (``sampling.LatentSampler``: forward-only walk, context K/V projected once, one fused
@@ -332,13 +333,25 @@ class StableDiffusion(ComposerModel):
         (the reference's loop in torch ops around ``unet(...)``); default ``DA_SAMPLER``, else ``'hip'``.
 
         ``inference_scheduler``: the solver of this call only: ``'ddim'``, ``'dpm++2m'`` (``DPMSolverMultistepScheduler``
-        on the model's noise tables) or a scheduler object; default the model's own (``self.inference_scheduler``)."""
+        on the model's noise tables) or a scheduler object; default the model's own (``self.inference_scheduler``).
+
+        ``init_image`` (image-to-image): floats in [0, 1] (what this method returns), [B, 3, H, W] or [1, 3, H, W] for the
+        whole batch; ``height`` / ``width`` default to its size.  It is encoded by the VAE (``z0 = 0.18215 *
+        latent_dist.sample()``: the call's generator draws the posterior sample first, the noise second), noised to an
+        intermediate timestep and only the last ``int(num_inference_steps * strength)`` steps run; ``strength`` in (0, 1].
+        ``mask`` (inpainting, needs ``init_image``): [H, W], [1, 1, H, W] or [B, 1, H, W] in [0, 1], 1 = repaint, 0 = keep,
+        fractions blend; after every step the latent outside the mask is replaced by ``z0`` re-noised to the level of the
+        next timestep (the 4-channel scheme of diffusers' ``StableDiffusionInpaintPipeline``).  Kept areas come back through
+        the VAE round trip: there is no pixel-space composite after decoding.  Every ``sampler=`` route takes them."""
         sampler = resolve_sampler(sampler)
         check_inference_scheduler(inference_scheduler)
         _check_prompt_given(prompt, tokenized_prompts, prompt_embeds)
         _check_prompt_lenths(prompt, negative_prompt)
         _check_prompt_lenths(tokenized_prompts, tokenized_negative_prompts)
         _check_prompt_lenths(prompt_embeds, negative_prompt_embeds)
+        height, width, start_index = _check_init_image(
+            init_image, strength, mask, height, width, num_inference_steps,
+            _prompt_batch(prompt, tokenized_prompts, prompt_embeds) * num_images_per_prompt)
         device = self.unet.device_
         rng = torch.Generator(device=device)
         if seed:
@@ -359,17 +372,32 @@ class StableDiffusion(ComposerModel):
                                                    num_images_per_prompt)
             if sampler == 'torch':
                 text_embeddings = torch.cat([uncond, text_embeddings])
+        z0 = mask_px = None
+        if init_image is not None:   # the posterior sample is drawn before the noise
+            z0 = self._encode_init_image(init_image, batch_size, rng)
+            if mask is not None:
+                mask_px = mask.to(device, torch.float32).reshape(-1, height, width).expand(batch_size, -1, -1).contiguous()
         latents = torch.randn((batch_size, self.unet.config.in_channels, height // vae_scale, width // vae_scale),
                               device=device, generator=rng)
         scheduler = resolve_inference_scheduler(inference_scheduler, self.inference_scheduler)
         scheduler.set_timesteps(num_inference_steps)
         latents = latents * scheduler.init_noise_sigma
         if sampler != 'torch':
+            partial = {} if z0 is None else dict(known=z0, start_index=start_index, mask_px=mask_px)
             latents = LatentSampler(self.unet, scheduler).sample(
                 latents, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
-                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar)
+                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar, **partial)
         else:   # the reference's loop, the scheduler step in torch ops
-            for t in tqdm(scheduler.timesteps, disable=not progress_bar):
+            timesteps = scheduler.timesteps
+            if z0 is not None:   # the same method in torch ops: start from the noised image, run the tail of the schedule
+                noise = latents
+                latents = scheduler.add_noise(z0, noise, timesteps[start_index:start_index + 1])
+                if start_index and hasattr(scheduler, 'set_begin_index'):
+                    scheduler.set_begin_index(start_index)
+                if mask_px is not None:
+                    m = F.avg_pool2d(mask_px[:, None], vae_scale)
+            for i in tqdm(range(start_index, len(timesteps)), disable=not progress_bar):
+                t = timesteps[i]
                 lin = torch.cat([latents] * 2) if do_cfg else latents
                 lin = scheduler.scale_model_input(lin, t)
                 pred = self.unet(lin, t, encoder_hidden_states=text_embeddings).sample
@@ -377,6 +405,9 @@ class StableDiffusion(ComposerModel):
                     pu, pt = pred.chunk(2)
                     pred = pu + guidance_scale * (pt - pu)
                 latents = scheduler.step(pred, t, latents, generator=rng)['prev_sample']
+                if mask_px is not None:   # outside the mask: the known latent at the noise level of the next timestep
+                    kn = scheduler.add_noise(z0, noise, timesteps[i + 1:i + 2]) if i + 1 < len(timesteps) else z0
+                    latents = m * latents + (1 - m) * kn
         latents = 1 / 0.18215 * latents
         # image decoder: the HIP-kernel walk of the same frozen weights when the factory built one (models/vae_hip.py),
         # else the PyTorch-ROCm module
@@ -388,6 +419,20 @@ class StableDiffusion(ComposerModel):
             image = self.vae.decode(latents.to(vdtype)).sample
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.detach().float()
+
+    def _encode_init_image(self, init_image, batch_size, rng):
+        """``generate(init_image=...)``: [0, 1] images -> z0 = 0.18215 * latent_dist.sample(generator=rng), [B, C, h, w] fp32,
+        through the HIP VAE encoder when the factory built one, else the PyTorch-ROCm module (as ``_encode`` does)."""
+        if self.vae is None:
+            raise RuntimeError('this model was built without a VAE; init_image needs one')
+        device = self.unet.device_
+        img = (init_image.to(device, torch.float32) * 2 - 1).expand(batch_size, -1, -1, -1)
+        vae_hip = getattr(self, 'vae_hip', None)
+        if vae_hip is not None:
+            dist = vae_hip.encode(img)['latent_dist']
+        else:
+            dist = self.vae.encode(img.to(next(self.vae.parameters()).dtype))['latent_dist']
+        return (0.18215 * dist.sample(generator=rng)).float()
 
     def _prepare_text_embeddings(self, prompt, tokenized_prompts, prompt_embeds, num_images_per_prompt):
         device = self.unet.device_
@@ -412,6 +457,41 @@ def _check_prompt_lenths(prompt, negative_prompt):
         if negative_prompt_bs != batch_size:
             raise ValueError(f'len(prompts) and len(negative_prompts) must be the same. '
                              f'A negative prompt must be provided for each given prompt.')
+
+
+def _prompt_batch(prompt, tokenized_prompts, prompt_embeds):
+    """The number of prompts, in the precedence ``_prepare_text_embeddings`` reads them."""
+    for p in (prompt_embeds, tokenized_prompts, prompt):
+        if p is not None:
+            return 1 if isinstance(p, str) else len(p)
+
+
+def _check_init_image(init_image, strength, mask, height, width, num_inference_steps, batch_size):
+    """The checks of ``generate(init_image=..., strength=..., mask=...)``, all on the host: (height, width, start_index).
+    Without an image: (height, width, 0) as given."""
+    if init_image is None:
+        if mask is not None:
+            raise ValueError('generate: mask needs init_image, the image whose unmasked part is kept')
+        return height, width, 0
+    if not isinstance(init_image, torch.Tensor) or not init_image.is_floating_point() or init_image.dim() != 4 \
+            or init_image.shape[1] != 3 or init_image.shape[0] not in (1, batch_size):
+        raise ValueError(f'generate: init_image must be floats in [0, 1], [{batch_size}, 3, H, W] or [1, 3, H, W]')
+    H, W = init_image.shape[-2:]
+    if (height is not None and height != H) or (width is not None and width != W):
+        raise ValueError(f'generate: height x width {height} x {width} differ from init_image\'s {H} x {W}')
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f'generate: strength must lie in (0, 1], got {strength}')
+    n_run = min(int(num_inference_steps * strength), num_inference_steps)
+    if n_run == 0:
+        raise ValueError(f'generate: strength {strength} runs no step of {num_inference_steps}')
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_floating_point() \
+                or tuple(mask.shape) not in ((H, W), (1, 1, H, W), (batch_size, 1, H, W)):
+            raise ValueError(f'generate: mask must be floats in [0, 1], [{H}, {W}], [1, 1, {H}, {W}] or '
+                             f'[{batch_size}, 1, {H}, {W}], got {tuple(getattr(mask, "shape", ()))}')
+        if not bool(((mask >= 0) & (mask <= 1)).all()):
+            raise ValueError('generate: mask values must lie in [0, 1] (1 = repaint, 0 = keep)')
+    return H, W, num_inference_steps - n_run
 
 
 def _check_prompt_given(prompt, tokenized_prompts, prompt_embeds):

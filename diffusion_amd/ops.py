@@ -703,6 +703,121 @@ def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1
               xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
 
 
+def _blend_operands(fn, known8, eps8, mask, npix):
+    for z, nm in ((known8, 'known8'), (eps8, 'eps8')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (npix, 8) or z.data_ptr() % 16:
+            raise ValueError(f'{fn}: {nm} must be a contiguous fp32 [{npix}, 8] device tensor, 16-byte aligned')
+    if mask.dtype != F32 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (npix,) \
+            or mask.data_ptr() % 16:
+        raise ValueError(f'{fn}: mask must be a contiguous fp32 [{npix}] device tensor, 16-byte aligned')
+
+
+def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, noise=None, *, C, cfg, copies=1):
+    """``sampler_step`` for a masked sample (``da_sampler_step_blend``): with v what ``sampler_step`` stores and m the pixel's
+    mask value, x_out = m v + (1 - m) (bA known8 + bS eps8).  ``coef`` = {cx, cm, cn, guidance, bA, bS, 0, 0} on the device.
+
+    known8 / eps8 fp32 [npix, 8] and mask fp32 [npix] (what ``sampler_init`` writes); the rest as in ``sampler_step``."""
+    C, copies, cfg = int(C), int(copies), bool(cfg)
+    if not 1 <= C <= 8 or copies not in (1, 2):
+        raise ValueError(f'sampler_step_blend: C = {C} (1..8), copies = {copies} (1 or 2)')
+    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
+        raise ValueError('sampler_step_blend: x must be [npix, 8]')
+    npix = x.shape[0]
+    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (x_out, npix, 'x_out')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
+            raise ValueError(f'sampler_step_blend: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
+    _blend_operands('sampler_step_blend', known8, eps8, mask, npix)
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
+        raise ValueError('sampler_step_blend: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
+    HW = npix
+    if noise is not None:
+        if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
+                or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
+            raise ValueError(f'sampler_step_blend: noise must be a contiguous fp32 [B, {C}, H, W] device tensor over {npix} '
+                             'pixels')
+        HW = noise.shape[2] * noise.shape[3]
+    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
+                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
+        raise ValueError(f'sampler_step_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    _lib.call('da_sampler_step_blend', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
+              coef.data_ptr(), known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
+              xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg), copies, _stream())
+
+
+def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out=None, *, C, cfg, copies=1):
+    """``sampler_step_ms`` for a masked sample (``da_sampler_step_ms_blend``): the same blend after the two-step update;
+    ``hist`` receives the unblended data prediction.  ``coef`` = {ax, am, kx, k0, k1, guidance, bA, bS} on the device."""
+    C, copies, cfg = int(C), int(copies), bool(cfg)
+    if not 1 <= C <= 8 or copies not in (1, 2):
+        raise ValueError(f'sampler_step_ms_blend: C = {C} (1..8), copies = {copies} (1 or 2)')
+    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
+        raise ValueError('sampler_step_ms_blend: x must be [npix, 8]')
+    npix = x.shape[0]
+    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (hist, npix, 'hist'), (x_out, npix, 'x_out')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
+            raise ValueError(f'sampler_step_ms_blend: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte '
+                             'aligned')
+    _blend_operands('sampler_step_ms_blend', known8, eps8, mask, npix)
+    if hist.data_ptr() in (x.data_ptr(), x_out.data_ptr(), pred.data_ptr(), known8.data_ptr(), eps8.data_ptr()):
+        raise ValueError('sampler_step_ms_blend: hist must be a buffer of its own')
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
+        raise ValueError('sampler_step_ms_blend: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
+    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
+                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
+        raise ValueError(f'sampler_step_ms_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    _lib.call('da_sampler_step_ms_blend', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
+              known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
+              xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
+
+
+def sampler_init(known, noise, coef, x, xt=None, *, known8=None, eps8=None, mask_px=None, mask=None, copies=1):
+    """The start of a sample that begins from an image (``da_sampler_init``): x = a0 known + s0 noise in NHWC-8 with its bf16
+    copies, and for a masked sample the NHWC-8 relayouts of both operands and the mask's f x f box mean.
+
+    known / noise fp32 NCHW [B, C, H, W]; coef = {a0, s0, 0, 0} on the device; x fp32 [B H W, 8]; xt None or bf16
+    [copies * B H W, 8]; known8 / eps8 None (both) or fp32 [B H W, 8]; mask_px None or fp32 [B, f H, f W] with f a power of
+    two in 1..16, and mask fp32 [B H W] given iff mask_px is."""
+    copies = int(copies)
+    if known.dim() != 4 or not 1 <= known.shape[1] <= 8 or known.numel() < 1 or copies not in (1, 2):
+        raise ValueError(f'sampler_init: known must be [B, C, H, W] with C in 1..8, copies = {copies} (1 or 2)')
+    B, C, H, W = known.shape
+    npix = B * H * W
+    for z, nm in ((known, 'known'), (noise, 'noise')):
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or z.shape != known.shape or z.data_ptr() % 16:
+            raise ValueError(f'sampler_init: {nm} must be a contiguous fp32 {tuple(known.shape)} device tensor, 16-byte aligned')
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 4 or coef.data_ptr() % 16:
+        raise ValueError('sampler_init: coef must be 4 contiguous fp32 on the device, 16-byte aligned')
+    if (known8 is None) != (eps8 is None) or (mask_px is None) != (mask is None):
+        raise ValueError('sampler_init: known8 goes with eps8, mask_px with mask')
+    for z, nm in ((x, 'x'), (known8, 'known8'), (eps8, 'eps8')):
+        if z is not None and (z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (npix, 8)
+                              or z.data_ptr() % 16):
+            raise ValueError(f'sampler_init: {nm} must be a contiguous fp32 [{npix}, 8] device tensor, 16-byte aligned')
+    if xt is not None and (xt.dtype != BF16 or not xt.is_cuda or not xt.is_contiguous()
+                           or tuple(xt.shape) != (copies * npix, 8) or xt.data_ptr() % 16):
+        raise ValueError(f'sampler_init: xt must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    f = 1
+    if mask_px is not None:
+        f = mask_factor(tuple(mask_px.shape), B, H, W, 'sampler_init')
+        if mask_px.dtype != F32 or not mask_px.is_cuda or not mask_px.is_contiguous() or mask_px.data_ptr() % 16:
+            raise ValueError(f'sampler_init: mask_px must be a contiguous fp32 [{B}, f {H}, f {W}] device tensor, 16-byte aligned')
+        if mask.dtype != F32 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (npix,) \
+                or mask.data_ptr() % 16:
+            raise ValueError(f'sampler_init: mask must be a contiguous fp32 [{npix}] device tensor, 16-byte aligned')
+    _lib.call('da_sampler_init', known.data_ptr(), noise.data_ptr(), mask_px.data_ptr() if mask_px is not None else None,
+              coef.data_ptr(), known8.data_ptr() if known8 is not None else None,
+              eps8.data_ptr() if eps8 is not None else None, mask.data_ptr() if mask is not None else None, x.data_ptr(),
+              xt.data_ptr() if xt is not None else None, B, H, W, C, f, copies, _stream())
+
+
+def mask_factor(shape, B, H, W, who='mask_px'):
+    """f of a pixel mask [B, f H, f W] over a [B, ., H, W] state: a power of two in 1..16 (``ValueError`` otherwise)."""
+    if len(shape) != 3 or shape[0] != B or H < 1 or W < 1 or shape[1] % H or shape[2] % W or shape[1] // H != shape[2] // W \
+            or shape[1] // H not in (1, 2, 4, 8, 16):
+        raise ValueError(f'{who}: mask_px must be [{B}, f * {H}, f * {W}] with f a power of two in 1..16, got {tuple(shape)}')
+    return shape[1] // H
+
+
 def add_noise(x0, eps, t, sqrt_ac, sqrt_1mac, xt, target, v_pred):
     B = x0.shape[0]
     HW = x0.shape[2] * x0.shape[3]

@@ -11,6 +11,10 @@ step
 A two-step scheduler (``scheduler.multistep``: ``DPMSolverMultistepScheduler``) is the same design one operand wider: the
 launch is ``ops.sampler_step_ms``, its rows are the eight floats of ``step_coefficients_ms`` and it carries the previous
 step's data prediction in a history buffer of the state's shape.
+A sample may start from an image (``sample(known=...)``: image-to-image): ``ops.sampler_init`` noises the known sample to
+the level of timestep ``start_index`` in one launch and only the tail of the schedule runs.  With a pixel mask
+(``mask_px``: inpainting) every step is the blended launch (``ops.sampler_step_blend`` / ``ops.sampler_step_ms_blend``),
+which replaces the state outside the mask by the known sample re-noised to the level of the next timestep.
 Nothing in the loop reads the device back.  ``graph=True`` replays one captured step (walk + ``sampler_step``) per
 denoising step, as ``graph_step.GraphedMicrobatch`` does for a training microbatch; the host then issues two 16-byte-class
 copies (the step's timestep and coefficient rows) and a replay.
@@ -45,15 +49,20 @@ class GraphedSamplerStep:
     """One captured denoising step for one signature: forward-only walk + ``sampler_step`` over static buffers."""
 
     def __init__(self, unet, rows: int, B: int, HW, C: int, cfg: bool, t_dtype, ctx: torch.Tensor, kv: dict,
-                 multistep: bool = False):
+                 multistep: bool = False, blend: bool = False):
         dev = unet.device_
         H, W = HW
         self.unet, self.rows, self.HW, self.C, self.cfg, self.multistep = unet, rows, (H, W), C, cfg, multistep
+        self.blend = blend
         npix = B * H * W
         self.x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
         self.xt = torch.zeros(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
         self.t = torch.zeros(rows, device=dev, dtype=t_dtype)
-        self.coef = torch.zeros(8 if multistep else 4, device=dev, dtype=torch.float32)
+        self.coef = torch.zeros(8 if multistep or blend else 4, device=dev, dtype=torch.float32)
+        # a masked sample: the known sample, its noise draw and the mask, written by sampler_init before the first replay
+        self.known8 = torch.zeros(npix, 8, device=dev, dtype=torch.float32) if blend else None
+        self.eps8 = torch.zeros(npix, 8, device=dev, dtype=torch.float32) if blend else None
+        self.mask = torch.zeros(npix, device=dev, dtype=torch.float32) if blend else None
         # the previous step's data prediction; k1 arrives through `coef`, so the one capture serves both orders
         self.hist = torch.zeros(npix, 8, device=dev, dtype=torch.float32) if multistep else None
         self.ctx = ctx.clone()
@@ -73,6 +82,10 @@ class GraphedSamplerStep:
 
     def _body(self):
         pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.HW, kv=self.kv, record=False)
+        if self.blend:
+            _blended_step(pred, self.x, self.hist, self.coef, self.known8, self.eps8, self.mask, self.xt, None, C=self.C,
+                          cfg=self.cfg, copies=2 if self.cfg else 1)
+            return
         if self.multistep:
             ops.sampler_step_ms(pred, self.x, self.hist, self.coef, self.x, self.xt, C=self.C, cfg=self.cfg,
                                 copies=2 if self.cfg else 1)
@@ -89,6 +102,14 @@ class GraphedSamplerStep:
         self.t.copy_(t_row, non_blocking=True)
         self.coef.copy_(coef_row, non_blocking=True)
         self.graph.replay()
+
+
+def _blended_step(pred, x, hist, coef, known8, eps8, mask, xt, noise, **kw):
+    """One masked step in place: the two-step form when there is a history buffer, else the first-order one."""
+    if hist is not None:
+        ops.sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x, xt, **kw)
+    else:
+        ops.sampler_step_blend(pred, x, coef, known8, eps8, mask, x, xt, noise, **kw)
 
 
 class LatentSampler:
@@ -117,12 +138,34 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, latents: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor] = None, *,
                num_inference_steps: int, guidance_scale: float, graph: bool = False,
-               progress_bar: bool = False) -> torch.Tensor:
+               progress_bar: bool = False, known: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+               start_index: int = 0, mask_px: Optional[torch.Tensor] = None) -> torch.Tensor:
         """latents: the initial noise [B, C, H, W] (already scaled by ``init_noise_sigma``); cond / uncond: [B, L, D] text
         states.  Classifier-free guidance runs iff ``guidance_scale > 1.0`` (``uncond`` is then required).  Returns the
-        denoised [B, C, H, W] fp32 (latent models: before the 1 / 0.18215 rescale)."""
+        denoised [B, C, H, W] fp32 (latent models: before the 1 / 0.18215 rescale).
+
+        ``known`` (image-to-image): the clean sample [B, C, H, W] to start from (latent models: already scaled by 0.18215).
+        It is noised with ``noise`` (default ``latents``, which may then be None) to the level of timestep number
+        ``start_index`` and steps ``start_index .. n - 1`` run; discrete-time schedulers only.  ``mask_px`` (inpainting,
+        needs ``known``): fp32 [B, f H, f W] in [0, 1] at f x f pixels per state pixel (f a power of two in 1..16; 8 for the
+        latent models), 1 = repaint, 0 = keep; its f x f box mean weighs every step's blend with the re-noised known
+        sample.  Every check of these raises ``ValueError`` before anything is launched."""
         unet, sch = self.unet, self.scheduler
-        dev = unet.device_
+        if known is None:
+            if mask_px is not None:
+                raise ValueError('mask_px needs known: the sample whose unmasked part is kept')
+            if noise is not None or start_index != 0:
+                raise ValueError('noise and start_index go with known')
+        else:
+            if noise is None:
+                noise = latents
+            if noise is None or known.dim() != 4 or tuple(noise.shape) != tuple(known.shape):
+                raise ValueError('known and noise (default: latents) must both be [B, C, H, W]')
+            if latents is not None and tuple(latents.shape) != tuple(known.shape):
+                raise ValueError(f'latents {tuple(latents.shape)} and known {tuple(known.shape)} differ in shape')
+            if mask_px is not None:
+                ops.mask_factor(tuple(mask_px.shape), known.shape[0], known.shape[2], known.shape[3], 'sample')
+            latents = noise
         B, C, H, W = latents.shape
         unet.check_spatial(H, W)
         if C != unet.cfg.in_channels:
@@ -140,16 +183,31 @@ class LatentSampler:
         multistep = bool(getattr(sch, 'multistep', False))
         if multistep and continuous:
             raise ValueError('a multistep scheduler is a discrete-time method')
+        blend = mask_px is not None
+        if known is not None:
+            if continuous or not hasattr(sch, 'add_noise_coefficients'):
+                raise ValueError('a sample that starts from known needs a discrete-time scheduler (add_noise_coefficients)')
+            if not 0 <= int(start_index) < n:
+                raise ValueError(f'start_index must lie in [0, {n}), got {start_index}')
+        start = int(start_index)
+        dev = unet.device_
         # per-call device tables, one upload each: the timestep of every step for every row, {cx, cm, cn, guidance}
         # (a two-step scheduler: {ax, am, kx, k0, k1, guidance, 0, 0}, and no noise term)
         t_tab = torch.tensor(ts, dtype=torch.float64 if continuous else torch.int64).to(t_dtype)[:, None] \
             .expand(n, rows).contiguous().to(dev)
+        # a masked sample: (bA, bS) re-noises the known sample to the level of the next timestep; the last step keeps it clean
+        renoise = [(sch.add_noise_coefficients(ts[i + 1]) if i + 1 < n else (1.0, 0.0)) if blend else (0.0, 0.0)
+                   for i in range(n)]
         if multistep:
-            coef_rows = [list(sch.step_coefficients_ms(i)) + [float(guidance_scale), 0.0, 0.0] for i in range(n)]
+            # the first executed step of a schedule entered late has no history: first order
+            first = [known is not None and i == start for i in range(n)]
+            coef_rows = [list(sch.step_coefficients_ms(i, first=True) if first[i] else sch.step_coefficients_ms(i))
+                         + [float(guidance_scale), *renoise[i]] for i in range(n)]
             stochastic = False
         else:
             coefs = [sch.step_coefficients(t) for t in ts]
-            coef_rows = [[cx, cm, cn, float(guidance_scale)] for cx, cm, cn in coefs]
+            coef_rows = [[cx, cm, cn, float(guidance_scale)] + ([*renoise[i], 0.0, 0.0] if blend else [])
+                         for i, (cx, cm, cn) in enumerate(coefs)]
             stochastic = any(cn != 0.0 for _, _, cn in coefs)
         coef_tab = torch.tensor(coef_rows, dtype=torch.float64).to(torch.float32).to(dev)
         # the context: cast once, projected once
@@ -159,25 +217,41 @@ class LatentSampler:
         copies = 2 if cfg else 1
         g = None
         if graph and not stochastic and ops.PROFILE is None:   # the SDE needs a fresh draw per step: eager
-            key = (rows, H, W, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1]) + (('multistep',) if multistep else ())
-            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep)
+            key = (rows, H, W, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1]) + (('multistep',) if multistep else ()) \
+                + (('blend',) if blend else ())
+            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep, blend)
             g.load(ctx, kv)
             x, xt, hist = g.x, g.xt, g.hist
+            known8, eps8, mask = g.known8, g.eps8, g.mask
             x.zero_()
         else:
             x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
             xt = torch.empty(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
             # the first step is first order (k1 = 0) and does not read it: no fill
             hist = torch.empty(npix, 8, device=dev, dtype=torch.float32) if multistep else None
-        # NCHW -> NHWC-8 of the initial noise (and its bf16 copies) by the step kernel itself: 0 x + 0 m + 1 z
+            known8 = torch.empty(npix, 8, device=dev, dtype=torch.float32) if blend else None
+            eps8 = torch.empty(npix, 8, device=dev, dtype=torch.float32) if blend else None
+            mask = torch.empty(npix, device=dev, dtype=torch.float32) if blend else None
         lat = latents.to(dev, torch.float32).contiguous()
-        one = torch.tensor([0.0, 0.0, 1.0, 0.0], device=dev)
-        ops.sampler_step(x, x, one, x, xt, lat, C=C, cfg=False, copies=copies)
-        for i in tqdm(range(n), disable=not progress_bar):
+        if known is None:
+            # NCHW -> NHWC-8 of the initial noise (and its bf16 copies) by the step kernel itself: 0 x + 0 m + 1 z
+            one = torch.tensor([0.0, 0.0, 1.0, 0.0], device=dev)
+            ops.sampler_step(x, x, one, x, xt, lat, C=C, cfg=False, copies=copies)
+        else:
+            a0, s0 = sch.add_noise_coefficients(ts[start])
+            start_coef = torch.tensor([a0, s0, 0.0, 0.0], dtype=torch.float64).to(torch.float32).to(dev)
+            ops.sampler_init(known.to(dev, torch.float32).contiguous(), lat, start_coef, x, xt, known8=known8, eps8=eps8,
+                             mask_px=mask_px.to(dev, torch.float32).contiguous() if blend else None, mask=mask,
+                             copies=copies)
+        for i in tqdm(range(start, n), disable=not progress_bar):
             if g is not None:
                 g.step(t_tab[i], coef_tab[i])
                 continue
             pred = unet.forward_features(xt, t_tab[i], ctx, rows, (H, W), kv=kv, record=False)
+            if blend:   # discrete time: no noise draw
+                _blended_step(pred, x, hist, coef_tab[i], known8, eps8, mask, xt if i + 1 < n else None, None, C=C, cfg=cfg,
+                              copies=copies)
+                continue
             if multistep:
                 ops.sampler_step_ms(pred, x, hist, coef_tab[i], x, xt if i + 1 < n else None, C=C, cfg=cfg, copies=copies)
                 continue

@@ -289,6 +289,38 @@ int da_sampler_step(const float* pred, const float* x, const float* noise, const
  * da_sampler_step, and for a NULL or misaligned hist. */
 int da_sampler_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out, void* xt_out,
                        long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+/* The masked (inpainting) forms of both steps.  Everything as in da_sampler_step / da_sampler_step_ms, then, with v the
+ * value those would store and m the pixel's mask value (broadcast over the channels):
+ *   kn = bA known8 + bS eps8;   x_out = m v + (1 - m) kn  (in exactly this form);   xt = bf16(x_out)
+ *   known8 fp32 [npix][8], the clean sample, and eps8 fp32 [npix][8], its noise draw (da_sampler_init writes both);
+ *   mask   fp32 [npix]: 1 repaints the pixel, 0 keeps it, fractions blend;
+ *   coef   DEVICE pointer to eight floats: {cx, cm, cn, guidance, bA, bS, 0, 0} for da_sampler_step_blend,
+ *          {ax, am, kx, k0, k1, guidance, bA, bS} for da_sampler_step_ms_blend; (bA, bS) re-noises the known sample to the
+ *          level of the next timestep, (1, 0) on the last step.
+ * m == 1 stores v's bits, m == 0 stores kn's, and with (bA, bS) = (1, 0) kn is known8's bits, however the compiler contracts
+ * the FMAs (all operands finite).  hist of the two-step form is the unblended data prediction, as in da_sampler_step_ms.
+ * Every load of a pixel precedes its first store: x_out may be x.  DA_ERR_SHAPE as for the unmasked forms, and for a NULL or
+ * misaligned known8 / eps8 / mask. */
+int da_sampler_step_blend(const float* pred, const float* x, const float* noise, const float* coef, const float* known8,
+                          const float* eps8, const float* mask, float* x_out, void* xt_out, long npix, int HW, int C,
+                          int cfg, int copies, da_stream_t stream);
+int da_sampler_step_ms_blend(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
+                             const float* eps8, const float* mask, float* x_out, void* xt_out, long npix, int HW, int C,
+                             int cfg, int copies, da_stream_t stream);
+/* The start of a sample that begins from an image (image-to-image, inpainting), one launch:
+ *   known   fp32 NCHW [B][C][H][W], the clean sample (latent models: already scaled); noise the same shape;
+ *   mask_px NULL, or fp32 [B][f H][f W], the mask at f x f pixels per state pixel, f a power of two in 1..16;
+ *   coef    DEVICE pointer to four floats {a0, s0, 0, 0}: add_noise at the first executed timestep;
+ *   known8, eps8  NULL (both), or fp32 [B H W][8]: bit-exact NHWC-8 relayouts of known and noise;
+ *   mask    fp32 [B H W], given iff mask_px is: the f x f box mean, summed row by row from the top left (a fixed order) and
+ *           multiplied by the exact 1 / f^2;
+ *   x       fp32 [B H W][8] = a0 known + s0 noise;  xt NULL, or bf16 [copies * B H W][8] = bf16(x), `copies` (1 or 2) times.
+ * Channels C..7 of every [.][8] output are exactly 0.  DA_ERR_SHAPE for B, H or W <= 0, H W > 2^23, C outside 1..8, f no
+ * power of two in 1..16, copies outside {1, 2}, a NULL known / noise / coef / x, mask without mask_px or known8 without eps8
+ * (or the reverse), or a pointer that is not 16-byte aligned. */
+int da_sampler_init(const float* known, const float* noise, const float* mask_px, const float* coef, float* known8,
+                    float* eps8, float* mask, float* x, void* xt, int B, int H, int W, int C, int f, int copies,
+                    da_stream_t stream);
 
 /* LargestCenterSquare(R) + ToTensor + Normalize(0.5,0.5) of B packed RGB uint8 images (transforms.py:9-21, laion.py:159-164):
  * PIL's antialiased bilinear resize of the shorter side to R (the longer one to floor(R*long/short)), the centre crop with

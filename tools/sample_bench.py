@@ -3,7 +3,7 @@ step in torch ops), ``'hip'`` (``sampling.LatentSampler``) and ``'graph'`` (the 
 one JSON line.
 
   python tools/sample_bench.py [--batches 1,4,16] [--steps 20] [--px 256] [--guidance 3.0] [--seconds 6] [--model NAME]
-                                [--scheduler ddim|dpm++2m]
+                                [--scheduler ddim|dpm++2m] [--inpaint]
 
 SD-2-base U-Net, random init, precomputed text embeddings (no VAE, no text encoder: the loop alone), latents of
 ``px / 8``.  Per batch size B (2 B U-Net rows with guidance):
@@ -17,6 +17,9 @@ SD-2-base U-Net, random init, precomputed text embeddings (no VAE, no text encod
 ``--scheduler dpm++2m`` runs the three modes with ``DPMSolverMultistepScheduler`` and adds a fourth to the same rounds,
 ``ddim_hip`` (the ``'hip'`` mode with the DDIM scheduler), so that the per-step times of the two solvers come from
 interleaved calls of one session.
+``--inpaint`` adds ``inpaint`` to the same rounds: the ``'hip'`` mode as a masked sample (``sample(known=, mask_px=)``, a
+half-plane mask, ``start_index=0`` so that it runs the same ``--steps`` steps), i.e. one ``sampler_init`` launch and the
+blended step launch in place of the plain one.  ``ms_per_step_vs_hip`` is its median call over the unmasked ``'hip'`` one.
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=6.0)
     ap.add_argument('--model', default='stabilityai/stable-diffusion-2-base')
     ap.add_argument('--scheduler', default='ddim', choices=('ddim', 'dpm++2m'))
+    ap.add_argument('--inpaint', action='store_true')
     a = ap.parse_args()
 
     import torch
@@ -54,7 +58,7 @@ def main():
                                inference_scheduler=a.scheduler)
     unet, sch = model.unet, model.inference_scheduler
     sampler = LatentSampler(unet, sch)
-    modes = MODES + (('ddim_hip',) if a.scheduler != 'ddim' else ())
+    modes = MODES + (('ddim_hip',) if a.scheduler != 'ddim' else ()) + (('inpaint',) if a.inpaint else ())
     ddim_sampler = LatentSampler(unet, make_inference_scheduler('ddim', like=sch))
     S, D = a.px // 8, unet.cfg.cross_attention_dim
     cfg = a.guidance > 1.0
@@ -73,6 +77,9 @@ def main():
         return lat
 
     def run(mode, lat, txt, unc):
+        if mode == 'inpaint':
+            return sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance, known=known,
+                                  start_index=0, mask_px=mask_px)
         if mode == 'torch':
             return torch_loop(lat, txt, unc)
         if mode == 'ddim_hip':
@@ -85,6 +92,9 @@ def main():
         g = torch.Generator().manual_seed(100 + B)
         lat = torch.randn(B, unet.cfg.in_channels, S, S, generator=g).to(dev)
         txt, unc = torch.randn(B, 77, D, generator=g).to(dev), torch.randn(B, 77, D, generator=g).to(dev)
+        known = torch.randn(lat.shape, generator=g).to(dev)
+        mask_px = torch.zeros(B, a.px, a.px, device=dev)
+        mask_px[:, :, a.px // 2:] = 1.0   # repaint the right half
         row, outs, times = {'B': B}, {}, {m: [] for m in modes}
         sampler.graphs.clear()
         run('hip', lat, txt, unc)   # scratch and workspaces of this shape exist before any peak is read
@@ -112,11 +122,14 @@ def main():
             med = statistics.median(times[m])
             row[m].update(ms_per_step=round(med * 1e3 / a.steps, 3), images_per_s=round(B / med, 2), calls=len(times[m]),
                           spread=round((max(times[m]) - min(times[m])) / med, 3))
-            if m in MODES:   # ddim_hip is another solver: its latents are not comparable
+            if m in MODES:   # ddim_hip is another solver, inpaint another sample: their latents are not comparable
                 row[m]['rel_l2_vs_torch'] = float(f'{((outs[m].float() - ref).norm() / ref.norm()).item():.3e}')
         if 'ddim_hip' in modes:
             row['hip']['ms_per_step_vs_ddim_hip'] = round(statistics.median(times['hip']) /
                                                           statistics.median(times['ddim_hip']), 4)
+        if 'inpaint' in modes:
+            row['inpaint']['ms_per_step_vs_hip'] = round(statistics.median(times['inpaint']) /
+                                                         statistics.median(times['hip']), 4)
         for m in ('hip', 'graph'):
             row[m]['speedup_vs_torch'] = round(statistics.median(times['torch']) / statistics.median(times[m]), 3)
         res['batches'].append(row)
