@@ -55,6 +55,14 @@ def _rel(a, b):
     return ((a.float() - b.float()).norm() / (b.float().norm() + 1e-20)).item()
 
 
+def _worst_tensor(got, ref):
+    """(name, rel-L2) of the gradient tensor that is worst on its own, matrices and vectors alike (recorded, not asserted
+    here: test_walk_stress_gpu.py holds every tensor to a bound at weights where a wiring slip shows)."""
+    rel = {k: _rel(got[k], r) for k, r in ref.items() if r.norm() > 0}
+    k = max(rel, key=rel.get)
+    return k, rel[k]
+
+
 def test_param_count_and_state_dict_names(dev):
     from oracle import unet_oracle as O
     from diffusion_amd.models.unet import UNetConfig, UNetHIP
@@ -98,8 +106,9 @@ def test_tiny_train_step_parity(dev):
     numv = sum(((got[k] - grads_ref[k])**2).sum().item() for k in grads_ref if grads_ref[k].dim() == 1)
     denv = sum((grads_ref[k]**2).sum().item() for k in grads_ref if grads_ref[k].dim() == 1)
     vrel = math.sqrt(numv / denv)
+    wt = _worst_tensor(got, grads_ref)
     _record('tiny_s16_b2', TOL_TINY, pred_rel_l2=e, loss_abs_delta=dl, grad_rel_l2=grel, worst_matrix_cosine=worst[1],
-            worst_matrix=worst[0], vector_grads_rel_l2=vrel)
+            worst_matrix=worst[0], vector_grads_rel_l2=vrel, worst_tensor_rel_l2=wt[1], worst_tensor=wt[0])
     assert e < TOL_TINY['pred_rel'], f'eps-prediction rel-L2 {e}'
     assert dl < TOL_TINY['loss_abs'], (loss.item(), loss_ref.item())
     assert grel < TOL_TINY['grad_rel'], f'global grad rel-L2 {grel}'
@@ -168,9 +177,12 @@ def test_full_sd2_base_forward_and_grads(dev):
     torch.cuda.synchronize()
     num = den = 0.0
     worst = (1.0, None)
+    wt = (None, 0.0)
     for k, p in model.unet.named_parameters():
         g = p.grad.detach().float().cpu()
         r = grads_ref[k]
+        if r.norm() > 0 and _rel(g, r) > wt[1]:
+            wt = (k, _rel(g, r))
         num += ((g - r)**2).sum().item()
         den += (r**2).sum().item()
         if r.dim() >= 2 and r.norm() > 0:
@@ -179,7 +191,7 @@ def test_full_sd2_base_forward_and_grads(dev):
                 worst = (c, k)
     grel = math.sqrt(num / den)
     _record('full_width_s8_b1_all_686_gradients', TOL_FULL8, pred_rel_l2=e, loss_abs_delta=dl, grad_rel_l2=grel,
-            worst_matrix_cosine=worst[0], worst_matrix=worst[1])
+            worst_matrix_cosine=worst[0], worst_matrix=worst[1], worst_tensor_rel_l2=wt[1], worst_tensor=wt[0])
     assert e < TOL_FULL8['pred_rel'], f'eps rel-L2 {e}'
     assert dl < TOL_FULL8['loss_abs']
     assert grel < TOL_FULL8['grad_rel'], grel
