@@ -71,6 +71,12 @@ SIGNATURES = {
     'da_sampler_step_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_ms_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_init': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    'da_guidance_rescale': [_fp, _fp, _i, _f, _fp, _l, _i, _i, _vp],
+    'da_sampler_step_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_step_ms_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_step_blend_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_sampler_step_ms_blend_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_mse_loss_w': [_fp, _fp, _vp, _fp, _fp, _l, _i, _i, _ll, _fp, _i, _f, _f, _i, _vp],
     'da_mse_loss': [_fp, _fp, _vp, _fp, _fp, _l, _f, _f, _i, _vp],
     'da_mse_loss_c': [_fp, _fp, _vp, _fp, _fp, _l, _i, _f, _f, _i, _vp],
     'da_adamw': [_fp, _fp, _fp, _fp, _vp, _fp, _f, _l, _f, _f, _f, _f, _f, _i, _f, _vp],

@@ -259,6 +259,38 @@ __global__ void mse_partial_c_kernel(const float* pred, const float* target, bf1
   const float s = block_sum(acc);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
+// ---- the same loss with a weight per sample, looked up by the sample's timestep: w = wtab[t[pix / HW]] (Min-SNR weighting).
+// A sample boundary may fall anywhere in a block or in a thread's grid-stride sequence: the weight is looked up per pixel.
+// A timestep outside [0, T) is clamped into the table.  dpred = (d * w) * grad_coef and acc += w * (d * d), each product
+// rounded on its own: with a table of ones these are the bits of mse_partial_c_kernel.
+__global__ void mse_partial_w_kernel(const float* pred, const float* target, bf16* dpred, float* partial, long total_pix,
+                                     int C, int HW, const long long* t, const float* wtab, int T, float grad_coef) {
+  float acc = 0.f;
+  GRID_STRIDE(i, total_pix) {
+#pragma clang fp contract(off)
+    long long ts = t[i / HW];
+    ts = ts < 0 ? 0 : (ts >= T ? T - 1 : ts);
+    const float w = wtab[ts];
+    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), q0 = *reinterpret_cast<const f32x4*>(target + i * 8);
+    f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 0.f, 0.f};
+    if (C > 4) {  // uniform
+      p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
+      q1 = *reinterpret_cast<const f32x4*>(target + i * 8 + 4);
+    }
+    bf16x8 g = zero8();
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        float d = (c < 4 ? p0[c & 3] : p1[c & 3]) - (c < 4 ? q0[c & 3] : q1[c & 3]);
+        acc += w * (d * d);
+        g[c] = f2bf((d * w) * grad_coef);
+      }
+    }
+    st8(dpred + i * 8, g);
+  }
+  const float s = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
 __global__ void mse_finalize_kernel(const float* partial, int n, float* loss, float inv_count, float weight,
                                     int accumulate) {
   float acc = 0.f;
@@ -552,6 +584,22 @@ extern "C" int da_mse_loss_c(const float* pred, const float* target, void* dpred
                              long total_pix, int C, float grad_coef, float weight, int accumulate, hipStream_t s) {
   return mse_launch(pred, target, dpred, loss, scratch, total_pix, C, grad_coef,
                     (float)(1.0 / ((double)C * (double)total_pix)), weight, accumulate, s);
+}
+extern "C" int da_mse_loss_w(const float* pred, const float* target, void* dpred, float* loss, float* scratch,
+                             long total_pix, int C, int HW, const long long* t, const float* wtab, int T, float grad_coef,
+                             float weight, int accumulate, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (total_pix <= 0 || C < 1 || C > 8 || HW <= 0 || (total_pix % HW) || T <= 0 || !t || !wtab) return DA_ERR_SHAPE;
+  if ((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) & 15)) return DA_ERR_SHAPE;
+  int blocks = pw_blocks(total_pix);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(mse_partial_w_kernel, dim3(blocks), dim3(PW_BLOCK), 0, s, pred, target, (bf16*)dpred, scratch,
+                     total_pix, C, HW, t, wtab, T, grad_coef);
+  DA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(PW_BLOCK), 0, s, scratch, blocks, loss,
+                     (float)(1.0 / ((double)C * (double)total_pix)), weight, accumulate);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
 }
 extern "C" int da_adamw(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_smoothing,
                         long n, float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale,

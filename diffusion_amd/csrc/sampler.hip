@@ -36,12 +36,22 @@ struct Blend {
 template <>
 struct Blend<false> {};  // the unmasked kernels: the operand list they always had
 
+// Guidance rescale (Lin et al., arXiv:2305.08891, section 3.4): the guided prediction m of sample b is multiplied by
+// factor[b] (guidance_rescale_kernel below writes it) before the scheduler update.  hw is the sample's pixel count.
+template <bool RS>
+struct Rescale {
+  const float* factor;
+  int hw;
+};
+template <>
+struct Rescale<false> {};  // the plain kernels: the operand list and the arithmetic they always had
+
 // every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
 // BLEND: coef is the row widened to eight floats, {cx, cm, cn, guidance, bA, bS, 0, 0}
-template <bool BLEND>
-__global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
+template <bool BLEND, bool RS = false>
+__global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
     sampler_step_kernel(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, bf16* xt_out,
-                        long npix, int HW, int C, int cfg, int copies, Blend<BLEND> bl) {
+                        long npix, int HW, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
   const f32x4 k = *reinterpret_cast<const f32x4*>(coef);
   const float cx = k[0], cm = k[1], cn = k[2], g = k[3];
   float bA = 0.f, bS = 0.f;
@@ -68,6 +78,8 @@ __global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
     }
     const long b = i / HW;
     const int pix = (int)(i - b * HW);
+    float fac = 1.f;
+    if constexpr (RS) fac = rs.factor[i / rs.hw];
     float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -78,6 +90,7 @@ __global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
           const float pt = c < 4 ? q0[c & 3] : q1[c & 3];
           m = pu + g * (pt - pu);
         }
+        if constexpr (RS) m *= fac;
         float v = cx * xv + cm * m;
         if (noise) v += cn * noise[(b * C + c) * HW + pix];
         if constexpr (BLEND) v = mk * v + (1.f - mk) * kn[c];
@@ -105,10 +118,10 @@ __global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
 // k1 comes from device memory like the rest, so one captured launch serves first- and second-order steps alike.
 // every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
 // BLEND: coef = {ax, am, kx, k0, k1, guidance, bA, bS}
-template <bool BLEND>
-__global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
+template <bool BLEND, bool RS = false>
+__global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
     sampler_step_ms_kernel(const float* pred, const float* x, float* hist, const float* coef, float* x_out, bf16* xt_out,
-                           long npix, int C, int cfg, int copies, Blend<BLEND> bl) {
+                           long npix, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
   const f32x4 ka = *reinterpret_cast<const f32x4*>(coef), kb = *reinterpret_cast<const f32x4*>(coef + 4);
   const float ax = ka[0], am = ka[1], kx = ka[2], k0 = ka[3], k1 = kb[0], g = kb[1];
   const float bA = kb[2], bS = kb[3];  // the row's two free slots; read by the blended form only
@@ -135,6 +148,8 @@ __global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
 #pragma unroll
       for (int c = 0; c < 8; ++c) kn[c] = bA * (c < 4 ? n0[c & 3] : n1[c & 3]) + bS * (c < 4 ? e0[c & 3] : e1[c & 3]);
     }
+    float fac = 1.f;
+    if constexpr (RS) fac = rs.factor[i / rs.hw];
     float o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -145,6 +160,7 @@ __global__ void __launch_bounds__(BLEND ? SMP_BLOCK : SMP_MAX_BLOCK)
           const float pt = c < 4 ? q0[c & 3] : q1[c & 3];
           m = pu + g * (pt - pu);
         }
+        if constexpr (RS) m *= fac;
         const float dv = ax * xv + am * m;
         float v = kx * xv + k0 * dv;
         if (second) v += k1 * (c < 4 ? h0[c & 3] : h1[c & 3]);
@@ -219,7 +235,158 @@ __global__ void __launch_bounds__(SMP_BLOCK)
   }
 }
 
+// The statistics pass of guidance rescale: with pt the conditional half and m = pu + g (pt - pu), per sample b over its C
+// valid channels and HW pixels
+//   factor[b] = phi * std(pt) / std(m) + (1 - phi)          1 when std(m) == 0
+// One workgroup of 1024 threads per sample and no second launch: a sample is 256-768 KiB of pred, a few microseconds for one
+// CU beside a U-Net call of milliseconds, and a batch fills as many CUs as it has samples.  Both sums run in double on data
+// shifted by the sample's first value (sum (x - k), sum (x - k)^2: no cancellation however large |mean| / std is), pred is
+// read once, and the order is fixed: a thread's pixels in sequence, the wave butterfly, the 16 wave partials in wave order.
+constexpr int GR_BLOCK = 1024;
+__global__ void __launch_bounds__(GR_BLOCK)
+    guidance_rescale_kernel(const float* pred, const float* coef, int g_index, float phi, float* factor, long npix, int HW,
+                            int C) {
+  __shared__ double sh[GR_BLOCK / 64][4];
+  const float g = coef[g_index];
+  const float* pu_s = pred + (long)blockIdx.x * HW * 8;
+  const float* pt_s = pu_s + npix * 8;
+  // m itself is formed in double from the fp32 operands: the statistics then carry no rounding of m, which matters for
+  // samples of a few values; the step kernels' fp32 m differs from it by one rounding per element
+  const double gd = (double)g, kt = (double)pt_s[0], km = (double)pu_s[0] + gd * ((double)pt_s[0] - (double)pu_s[0]);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // sum (pt - kt), sum (pt - kt)^2, sum (m - km), sum (m - km)^2
+  for (int p = threadIdx.x; p < HW; p += GR_BLOCK) {
+    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pu_s + (long)p * 8), q0 = *reinterpret_cast<const f32x4*>(pt_s + (long)p * 8);
+    f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 0.f, 0.f};
+    if (C > 4) {  // uniform
+      p1 = *reinterpret_cast<const f32x4*>(pu_s + (long)p * 8 + 4);
+      q1 = *reinterpret_cast<const f32x4*>(pt_s + (long)p * 8 + 4);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        const float pu = c < 4 ? p0[c & 3] : p1[c & 3], pt = c < 4 ? q0[c & 3] : q1[c & 3];
+        const double m = (double)pu + gd * ((double)pt - (double)pu);
+        const double dt = (double)pt - kt, dm = m - km;
+        acc[0] += dt;
+        acc[1] += dt * dt;
+        acc[2] += dm;
+        acc[3] += dm * dm;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int w = 0; w < GR_BLOCK / 64; ++w)
+      for (int k = 0; k < 4; ++k) s[k] += sh[w][k];
+    const double n = (double)HW * (double)C;
+    const double vt = s[1] - s[0] * s[0] / n, vm = s[3] - s[2] * s[2] / n;  // n var; the count cancels in the ratio
+    double f = 1.0;
+    if (vm > 0.0) f = (double)phi * sqrt((vt > 0.0 ? vt : 0.0) / vm) + (1.0 - (double)phi);
+    factor[blockIdx.x] = (float)f;
+  }
+}
+
+template <bool BLEND, bool RS>
+int launch_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, void* xt_out,
+                long npix, int HW, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs, hipStream_t s) {
+  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL((sampler_step_kernel<BLEND, RS>), dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef,
+                     x_out, (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, bl, rs);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+template <bool BLEND, bool RS>
+int launch_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out, void* xt_out, long npix,
+                   int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs, hipStream_t s) {
+  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL((sampler_step_ms_kernel<BLEND, RS>), dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
+                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, bl, rs);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// the argument rules every step entry shares; `extra` ORs the form's own pointers, `need` is false when one of them is NULL
+bool step_args_ok(const float* pred, const float* x, const float* coef, float* x_out, void* xt_out, long npix, int HW, int C,
+                  int copies, uintptr_t extra, bool need) {
+  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return false;
+  if (!pred || !x || !coef || !x_out || !need) return false;
+  return !((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)coef | (uintptr_t)x_out | (uintptr_t)xt_out | extra) & 15));
+}
+
 }  // namespace
+
+extern "C" int da_guidance_rescale(const float* pred, const float* coef, int g_index, float phi, float* factor, long npix,
+                                   int HW, int C, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || g_index < 0 || g_index > 7) return DA_ERR_SHAPE;
+  if (!(phi >= 0.f && phi <= 1.f) || !pred || !coef || !factor) return DA_ERR_SHAPE;
+  if ((((uintptr_t)pred | (uintptr_t)coef) & 15) || ((uintptr_t)factor & 3)) return DA_ERR_SHAPE;
+  if (npix / HW > 0x7fffffffL) return DA_ERR_SHAPE;
+  hipLaunchKernelGGL(guidance_rescale_kernel, dim3((unsigned)(npix / HW)), dim3(GR_BLOCK), 0, s, pred, coef, g_index, phi,
+                     factor, npix, HW, C);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// ---- the four step forms with guidance rescale: `factor` fp32 [npix / HW] (4-byte aligned) multiplies m
+extern "C" int da_sampler_step_rs(const float* pred, const float* x, const float* noise, const float* coef,
+                                  const float* factor, float* x_out, void* xt_out, long npix, int HW, int C, int cfg,
+                                  int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies, (uintptr_t)noise, factor != nullptr) ||
+      ((uintptr_t)factor & 3))
+    return DA_ERR_SHAPE;
+  return launch_step<false, true>(pred, x, noise, coef, x_out, xt_out, npix, HW, C, cfg, copies, Blend<false>{},
+                                  Rescale<true>{factor, HW}, s);
+}
+
+extern "C" int da_sampler_step_ms_rs(const float* pred, const float* x, float* hist, const float* coef, const float* factor,
+                                     float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
+                                     hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies, (uintptr_t)hist, hist && factor) ||
+      ((uintptr_t)factor & 3))
+    return DA_ERR_SHAPE;
+  return launch_step_ms<false, true>(pred, x, hist, coef, x_out, xt_out, npix, C, cfg, copies, Blend<false>{},
+                                     Rescale<true>{factor, HW}, s);
+}
+
+extern "C" int da_sampler_step_blend_rs(const float* pred, const float* x, const float* noise, const float* coef,
+                                        const float* known8, const float* eps8, const float* mask, const float* factor,
+                                        float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
+                                        hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies,
+                    (uintptr_t)noise | (uintptr_t)known8 | (uintptr_t)eps8 | (uintptr_t)mask,
+                    known8 && eps8 && mask && factor) ||
+      ((uintptr_t)factor & 3))
+    return DA_ERR_SHAPE;
+  return launch_step<true, true>(pred, x, noise, coef, x_out, xt_out, npix, HW, C, cfg, copies,
+                                 Blend<true>{known8, eps8, mask}, Rescale<true>{factor, HW}, s);
+}
+
+extern "C" int da_sampler_step_ms_blend_rs(const float* pred, const float* x, float* hist, const float* coef,
+                                           const float* known8, const float* eps8, const float* mask, const float* factor,
+                                           float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
+                                           hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies,
+                    (uintptr_t)hist | (uintptr_t)known8 | (uintptr_t)eps8 | (uintptr_t)mask,
+                    hist && known8 && eps8 && mask && factor) ||
+      ((uintptr_t)factor & 3))
+    return DA_ERR_SHAPE;
+  return launch_step_ms<true, true>(pred, x, hist, coef, x_out, xt_out, npix, C, cfg, copies,
+                                    Blend<true>{known8, eps8, mask}, Rescale<true>{factor, HW}, s);
+}
 
 extern "C" int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out,
                                void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
@@ -231,7 +398,7 @@ extern "C" int da_sampler_step(const float* pred, const float* x, const float* n
   long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(sampler_step_kernel<false>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef, x_out,
-                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<false>{});
+                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<false>{}, Rescale<false>{});
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -246,7 +413,7 @@ extern "C" int da_sampler_step_ms(const float* pred, const float* x, float* hist
   long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(sampler_step_ms_kernel<false>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
-                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<false>{});
+                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<false>{}, Rescale<false>{});
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -263,7 +430,7 @@ extern "C" int da_sampler_step_blend(const float* pred, const float* x, const fl
   long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(sampler_step_kernel<true>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef, x_out,
-                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask});
+                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask}, Rescale<false>{});
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -280,7 +447,7 @@ extern "C" int da_sampler_step_ms_blend(const float* pred, const float* x, float
   long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(sampler_step_ms_kernel<true>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
-                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask});
+                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask}, Rescale<false>{});
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -24,8 +24,9 @@ import torch
 from .composer_shim import MeanSquaredError
 from ..schedulers.schedulers import ContinuousTimeScheduler
 from .pixel_diffusion import PixelDiffusion
+from ..sampling import check_guidance_rescale
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
-                         check_inference_scheduler, make_inference_scheduler)
+                         check_inference_scheduler, check_snr_gamma, check_timestep_spacing, make_inference_scheduler)
 from .stable_diffusion import StableDiffusion
 from .unet import UNetConfig, UNetHIP
 
@@ -73,6 +74,32 @@ def load_local_vae_weights(vae, directory: str):
     raise FileNotFoundError(f'no safetensors VAE weights under {directory}/vae')
 
 
+def _resolve_unet_config(model_name: str, unet_config: Optional[UNetConfig], probe: bool = False):
+    """The U-Net config of ``stable_diffusion_2``: the given one, the embedded one of a known name, SD-2-base's for a local
+    directory.  ``probe``: an unknown name gives SD-2-base's instead of raising (the early option checks only read
+    ``prediction_type``; the name is refused where it always was, after the device check)."""
+    if unet_config is not None:
+        return unet_config
+    if model_name in _KNOWN:
+        return _KNOWN[model_name]()
+    if probe or os.path.isdir(model_name):
+        return UNetConfig.sd2_base()
+    raise ValueError(f'unknown model_name {model_name!r}: known names {sorted(_KNOWN)} or a local directory')
+
+
+def _check_zero_snr_options(zero_terminal_snr, prediction_type, timestep_spacing, guidance_rescale, snr_gamma):
+    """The host-side checks of ``stable_diffusion_2``'s zero-terminal-SNR keywords, before the device is looked for: the
+    resolved ``timestep_spacing`` (None: ``'trailing'`` with ``zero_terminal_snr``, else ``'leading'``)."""
+    if zero_terminal_snr and prediction_type == 'epsilon':
+        raise ValueError("zero_terminal_snr: at the last timestep the input is pure noise, so an epsilon prediction says "
+                         "nothing about the sample; use a U-Net config with prediction_type 'v_prediction', got 'epsilon'")
+    check_guidance_rescale(guidance_rescale)
+    check_snr_gamma(snr_gamma)
+    if timestep_spacing is None:
+        return 'trailing' if zero_terminal_snr else 'leading'
+    return check_timestep_spacing(timestep_spacing)
+
+
 def stable_diffusion_2(
     model_name: str = 'stabilityai/stable-diffusion-2-base',
     pretrained: bool = True,
@@ -88,10 +115,22 @@ def stable_diffusion_2(
     unet_config: Optional[UNetConfig] = None,
     seed: int = 17,
     inference_scheduler: str = 'ddim',
+    zero_terminal_snr: bool = False,
+    snr_gamma: Optional[float] = None,
+    timestep_spacing: Optional[str] = None,
+    guidance_rescale: float = 0.0,
 ):
     """``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's)
-    or ``'dpm++2m'`` (``DPMSolverMultistepScheduler``)."""
+    or ``'dpm++2m'`` (``DPMSolverMultistepScheduler``).
+
+    ``zero_terminal_snr``: both schedulers rescale their betas so that the last timestep is pure noise (Lin et al.,
+    arXiv:2305.08891; ``rescale_betas_zero_snr``); needs a v-prediction U-Net config.  ``timestep_spacing``: the inference
+    grid, ``'leading'`` or ``'trailing'``; None means ``'trailing'`` with ``zero_terminal_snr``, else ``'leading'``.
+    ``guidance_rescale``: the model's default for ``generate()``.  ``snr_gamma``: Min-SNR-gamma loss weighting
+    (``StableDiffusion``).  What any of them does to image quality with trained weights has not been measured here."""
     check_inference_scheduler(inference_scheduler)
+    pt = _resolve_unet_config(model_name, unet_config, probe=True).prediction_type
+    timestep_spacing = _check_zero_snr_options(zero_terminal_snr, pt, timestep_spacing, guidance_rescale, snr_gamma)
     if train_metrics is None:
         train_metrics = [MeanSquaredError()]
     if val_metrics is None:
@@ -104,13 +143,7 @@ def stable_diffusion_2(
         raise RuntimeError('stable_diffusion_2: an MI355X is required (the U-Net has no CPU path)')
 
     local = model_name if os.path.isdir(model_name) else None
-    if unet_config is None:
-        if model_name in _KNOWN:
-            unet_config = _KNOWN[model_name]()
-        elif local:
-            unet_config = UNetConfig.sd2_base()
-        else:
-            raise ValueError(f'unknown model_name {model_name!r}: known names {sorted(_KNOWN)} or a local directory')
+    unet_config = _resolve_unet_config(model_name, unet_config)
     unet = UNetHIP(unet_config, device='cuda', seed=seed, init=True)
     if pretrained:
         if not local:
@@ -158,8 +191,11 @@ def stable_diffusion_2(
             from .text_hip import TextEncoderHIP
             text_hip = TextEncoderHIP(text_encoder)
         text_encoder = text_encoder.to(dtype)
-    noise_scheduler = DDPMScheduler(prediction_type=unet_config.prediction_type)
-    inference_noise_scheduler = make_inference_scheduler(inference_scheduler, prediction_type=unet_config.prediction_type)
+    noise_scheduler = DDPMScheduler(prediction_type=unet_config.prediction_type,
+                                    rescale_betas_zero_snr=bool(zero_terminal_snr))
+    inference_noise_scheduler = make_inference_scheduler(inference_scheduler, prediction_type=unet_config.prediction_type,
+                                                         rescale_betas_zero_snr=bool(zero_terminal_snr),
+                                                         timestep_spacing=timestep_spacing)
 
     model = StableDiffusion(
         unet=unet,
@@ -176,6 +212,8 @@ def stable_diffusion_2(
         precomputed_latents=precomputed_latents,
         encode_latents_in_fp16=encode_latents_in_fp16,
         fsdp=fsdp,
+        snr_gamma=snr_gamma,
+        guidance_rescale=guidance_rescale,
     )
     model.vae_hip = vae_hip if build_encoders else None
     model.vae_dec_hip = vae_dec_hip if build_encoders else None

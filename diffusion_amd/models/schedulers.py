@@ -11,17 +11,60 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
+
+TIMESTEP_SPACINGS = ('leading', 'trailing')
+# DPM-Solver++ at a table value of exactly 0 (zero terminal SNR): lambda = ln(alpha / sigma) is -inf there, so the value is
+# read as 2^-24, which is what diffusers' DPMSolverMultistepScheduler stores in its own table
+ZERO_SNR_ALPHA_CUMPROD = 2.0**-24
+
+
+def rescale_zero_terminal_snr(betas: torch.Tensor) -> torch.Tensor:
+    """Algorithm 1 of Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed" (arXiv:2305.08891), in
+    diffusers' operation order on the float32 betas: shift sqrt(abar) so that its last entry is 0, scale it so that its
+    first entry keeps its value, and turn the result back into betas.  abar_T comes out exactly 0 and beta_T exactly 1."""
+    s = torch.cumprod(1.0 - betas, dim=0).sqrt()
+    s0, sT = s[0].clone(), s[-1].clone()
+    s = s - sT
+    s = s * (s0 / (s0 - sT))
+    abar = s**2
+    alphas = torch.cat([abar[0:1], abar[1:] / abar[:-1]])
+    return 1.0 - alphas
+
+
+def check_timestep_spacing(spacing):
+    """``timestep_spacing=`` of the inference schedulers, the factory and ``generate()``: ``ValueError`` for anything but
+    the names of ``TIMESTEP_SPACINGS``."""
+    if spacing not in TIMESTEP_SPACINGS:
+        raise ValueError(f'timestep_spacing must be one of {TIMESTEP_SPACINGS}, got {spacing!r}')
+    return spacing
+
+
+def trailing_timesteps(num_train_timesteps: int, num_inference_steps: int) -> torch.Tensor:
+    """round(arange(T, 0, -T / n)) - 1 with numpy's round, as diffusers: the grid starts at T - 1."""
+    ts = np.round(np.arange(num_train_timesteps, 0, -num_train_timesteps / num_inference_steps)) - 1
+    return torch.from_numpy(ts.astype(np.int64))
+
+
+def _zero_snr_epsilon_error(t):
+    return ValueError(f'zero terminal SNR: alphas_cumprod[{t}] is 0, so an epsilon prediction says nothing about the sample '
+                      "there; a schedule with rescale_betas_zero_snr needs prediction_type 'v_prediction' (or 'sample'), "
+                      "got prediction_type 'epsilon'")
 
 
 class DDPMScheduler:
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
-                 beta_schedule: str = 'scaled_linear', prediction_type: str = 'epsilon', clip_sample: bool = False):
+                 beta_schedule: str = 'scaled_linear', prediction_type: str = 'epsilon', clip_sample: bool = False,
+                 rescale_betas_zero_snr: bool = False):
         if beta_schedule != 'scaled_linear':
             raise ValueError('SD-2 uses the scaled_linear schedule')
         self.num_train_timesteps = num_train_timesteps
         self.prediction_type = prediction_type
+        self.rescale_betas_zero_snr = bool(rescale_betas_zero_snr)
         self.betas = torch.linspace(beta_start**0.5, beta_end**0.5, num_train_timesteps, dtype=torch.float32)**2
+        if self.rescale_betas_zero_snr:
+            self.betas = rescale_zero_terminal_snr(self.betas)
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self._dev_tables = {}
@@ -59,12 +102,38 @@ class DDPMScheduler:
         return math.sqrt(ac), math.sqrt(1.0 - ac)
 
 
-class DDIMScheduler(DDPMScheduler):
+class _InferenceGrid:
+    """The timestep grid both inference schedulers walk.  ``'leading'`` (SD-2's): multiples of T // n plus ``steps_offset``,
+    clamped, and a step from t goes to t - T // n.  ``'trailing'`` (``trailing_timesteps``): the grid starts at T - 1 and a
+    step from grid entry i goes to entry i + 1, after the last entry to ``final_alpha_cumprod``.  For n that does not divide
+    T that is not t - T // n, where diffusers' DDIM steps off its own grid; here every step lands on the next timestep the
+    model is evaluated at."""
+
+    def _grid(self, num_inference_steps: int) -> torch.Tensor:
+        if self.timestep_spacing == 'trailing':
+            return trailing_timesteps(self.num_train_timesteps, num_inference_steps)
+        ratio = self.num_train_timesteps // num_inference_steps
+        return ((torch.arange(0, num_inference_steps) * ratio).flip(0) + self.steps_offset).clamp(
+            max=self.num_train_timesteps - 1)
+
+    def _prev_timestep(self, t: int) -> int:
+        """Where the step from timestep ``t`` lands; negative: past the end (``final_alpha_cumprod``)."""
+        if self.timestep_spacing != 'trailing':
+            return t - self.num_train_timesteps // self.num_inference_steps
+        grid = self.timesteps.tolist()
+        if t not in grid:
+            raise ValueError(f'timestep {t} is not on the current trailing grid of {len(grid)} steps')
+        i = grid.index(t)
+        return int(grid[i + 1]) if i + 1 < len(grid) else -1
+
+
+class DDIMScheduler(_InferenceGrid, DDPMScheduler):
     """eta = 0 DDIM sampler, ``set_alpha_to_one=False``, ``steps_offset=1`` (SD-2 scheduler_config.json)."""
 
-    def __init__(self, *a, steps_offset: int = 1, **kw):
+    def __init__(self, *a, steps_offset: int = 1, timestep_spacing: str = 'leading', **kw):
         super().__init__(*a, **kw)
         self.steps_offset = steps_offset
+        self.timestep_spacing = check_timestep_spacing(timestep_spacing)
         self.final_alpha_cumprod = self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
         self.timesteps = torch.arange(self.num_train_timesteps - 1, -1, -1)
@@ -72,10 +141,8 @@ class DDIMScheduler(DDPMScheduler):
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         self.num_inference_steps = num_inference_steps
-        ratio = self.num_train_timesteps // num_inference_steps
-        ts = (torch.arange(0, num_inference_steps) * ratio).flip(0) + self.steps_offset
-        self.timesteps = ts.clamp(max=self.num_train_timesteps - 1).to(device) if device is not None else ts.clamp(
-            max=self.num_train_timesteps - 1)
+        ts = self._grid(num_inference_steps)
+        self.timesteps = ts.to(device) if device is not None else ts
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -85,9 +152,11 @@ class DDIMScheduler(DDPMScheduler):
         (+ cn * noise, 0 for eta = 0).  The step is linear in both for each prediction type; ``prediction_type`` and
         ``num_inference_steps`` are read now, like ``step`` does.  What ``ops.sampler_step`` applies on the device."""
         t = int(timestep)
-        prev_t = t - self.num_train_timesteps // self.num_inference_steps
+        prev_t = self._prev_timestep(t)
         ac_t = float(self.alphas_cumprod[t])
         ac_prev = float(self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod)
+        if ac_t == 0.0 and self.prediction_type == 'epsilon':
+            raise _zero_snr_epsilon_error(t)
         a, s, A, S = math.sqrt(ac_t), math.sqrt(1 - ac_t), math.sqrt(ac_prev), math.sqrt(1 - ac_prev)
         if self.prediction_type == 'v_prediction':
             return A * a + S * s, S * a - A * s, 0.0
@@ -97,7 +166,9 @@ class DDIMScheduler(DDPMScheduler):
 
     def step(self, model_output, timestep, sample, generator=None, **kw):
         t = int(timestep)
-        prev_t = t - self.num_train_timesteps // self.num_inference_steps
+        prev_t = self._prev_timestep(t)
+        if float(self.alphas_cumprod[t]) == 0.0 and self.prediction_type == 'epsilon':
+            raise _zero_snr_epsilon_error(t)
         ac_t = self.alphas_cumprod[t].to(sample.device, sample.dtype)
         ac_prev = (self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod).to(sample.device, sample.dtype)
         if self.prediction_type == 'v_prediction':
@@ -117,11 +188,12 @@ class DDIMScheduler(DDPMScheduler):
         return _Out(prev_sample=prev)
 
 
-class DPMSolverMultistepScheduler(DDPMScheduler):
+class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
     """DPM-Solver++(2M) (Lu et al. 2022, arXiv:2211.01095, Algorithm 2): the second-order multistep solver of the diffusion ODE
     in the data-prediction parameterisation, deterministic, one model evaluation per step.  Same surface, timestep grid
-    (leading spacing, ``steps_offset``, clamped) and last step (to ``final_alpha_cumprod = alphas_cumprod[0]``, so lambda
-    stays finite) as ``DDIMScheduler``: both visit the same ``t``.
+    (``timestep_spacing``, ``steps_offset``) and last step (to ``final_alpha_cumprod = alphas_cumprod[0]``, so lambda
+    stays finite) as ``DDIMScheduler``: both visit the same ``t``.  A table value of exactly 0 (zero terminal SNR) is read
+    as 2^-24, as in diffusers, which keeps lambda finite there too.
 
     With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln(alpha / sigma), all from the fp32 ``alphas_cumprod`` table
     taken to float64, a step s -> t with h = lambda_t - lambda_s is
@@ -136,8 +208,10 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
 
     multistep = True
 
-    def __init__(self, *a, solver_order: int = 2, lower_order_final: bool = True, steps_offset: int = 1, **kw):
+    def __init__(self, *a, solver_order: int = 2, lower_order_final: bool = True, steps_offset: int = 1,
+                 timestep_spacing: str = 'leading', **kw):
         super().__init__(*a, **kw)
+        self.timestep_spacing = check_timestep_spacing(timestep_spacing)
         if solver_order not in (1, 2):
             raise ValueError(f'solver_order must be 1 or 2, got {solver_order}')
         if self.prediction_type not in ('epsilon', 'v_prediction', 'sample'):
@@ -163,9 +237,7 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         self.num_inference_steps = num_inference_steps
-        ratio = self.num_train_timesteps // num_inference_steps
-        ts = ((torch.arange(0, num_inference_steps) * ratio).flip(0) + self.steps_offset).clamp(
-            max=self.num_train_timesteps - 1)
+        ts = self._grid(num_inference_steps)
         self.timesteps = ts.to(device) if device is not None else ts
         self._reset()
 
@@ -175,6 +247,10 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
     def _alpha_sigma_lambda(self, t: int):
         """(alpha, sigma, lambda) in float64 at timestep ``t``; a negative ``t`` is past the end: ``final_alpha_cumprod``."""
         ac = float(self.alphas_cumprod[t] if t >= 0 else self.final_alpha_cumprod)
+        if ac == 0.0:
+            if self.prediction_type == 'epsilon':
+                raise _zero_snr_epsilon_error(t)
+            ac = ZERO_SNR_ALPHA_CUMPROD
         a, s = math.sqrt(ac), math.sqrt(1.0 - ac)
         return a, s, math.log(a / s)
 
@@ -197,10 +273,9 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
         exactly 0.0 on a first-order step.  ``prediction_type``, the order switches and the schedule are read now.
         ``first``: the step is the first one executed (a schedule entered at ``i`` > 0 has no history): first order."""
         i = int(i)
-        stride = self.num_train_timesteps // self.num_inference_steps
         t = int(self.timesteps[i])
         a_s, s_s, l_s = self._alpha_sigma_lambda(t)
-        a_t, s_t, l_t = self._alpha_sigma_lambda(t - stride)
+        a_t, s_t, l_t = self._alpha_sigma_lambda(self._prev_timestep(t))
         ax, am = self._data_prediction(a_s, s_s)
         h = l_t - l_s
         kd = -a_t * math.expm1(-h)
@@ -212,7 +287,7 @@ class DPMSolverMultistepScheduler(DDPMScheduler):
     def step(self, model_output, timestep, sample, generator=None, **kw):
         t = int(timestep)
         a_s, s_s, l_s = self._alpha_sigma_lambda(t)
-        a_t, s_t, l_t = self._alpha_sigma_lambda(t - self.num_train_timesteps // self.num_inference_steps)
+        a_t, s_t, l_t = self._alpha_sigma_lambda(self._prev_timestep(t))
         ax, am = self._data_prediction(a_s, s_s)
         x0 = ax * sample + am * model_output
         h = l_t - l_s
@@ -247,13 +322,15 @@ def check_inference_scheduler(scheduler, continuous_time: bool = False):
 
 def make_inference_scheduler(name: str, like=None, **kw):
     """The inference scheduler called ``name``.  With ``like`` (a ``DDPMScheduler`` of any kind) it walks that scheduler's
-    own noise tables with its ``prediction_type`` and ``steps_offset``, read now."""
+    own noise tables with its ``prediction_type``, ``steps_offset`` and ``timestep_spacing``, read now."""
     check_inference_scheduler(name)
     cls = INFERENCE_SCHEDULERS[name]
     if like is None:
         return cls(**kw)
+    kw.setdefault('timestep_spacing', getattr(like, 'timestep_spacing', 'leading'))
     sch = cls(num_train_timesteps=like.num_train_timesteps, prediction_type=like.prediction_type,
               steps_offset=getattr(like, 'steps_offset', 1), **kw)
+    sch.rescale_betas_zero_snr = getattr(like, 'rescale_betas_zero_snr', False)
     sch.betas, sch.alphas, sch.alphas_cumprod = like.betas, like.alphas, like.alphas_cumprod
     sch.final_alpha_cumprod = getattr(like, 'final_alpha_cumprod', like.alphas_cumprod[0])
     return sch
@@ -268,3 +345,58 @@ def resolve_inference_scheduler(scheduler, own, continuous_time: bool = False):
     if isinstance(scheduler, str):
         return own if type(own) is INFERENCE_SCHEDULERS[scheduler] else make_inference_scheduler(scheduler, like=own)
     return scheduler
+
+
+def with_timestep_spacing(scheduler, spacing):
+    """``generate(timestep_spacing=...)``: ``scheduler`` itself for None or its own spacing, else a shallow copy (same noise
+    tables) that walks the other grid for this call.  ``ValueError`` for an unknown name, and for a scheduler that has no
+    discrete grid to respace."""
+    if spacing is None:
+        return scheduler
+    check_timestep_spacing(spacing)
+    if not hasattr(scheduler, 'timestep_spacing'):
+        raise ValueError(f'timestep_spacing: {type(scheduler).__name__} has no discrete timestep grid to respace')
+    if scheduler.timestep_spacing == spacing:
+        return scheduler
+    import copy
+    sch = copy.copy(scheduler)
+    sch.timestep_spacing = spacing
+    return sch
+
+
+def check_zero_snr_grid(scheduler):
+    """After ``set_timesteps``: ``ValueError`` if an epsilon-prediction scheduler is about to visit a timestep whose
+    ``alphas_cumprod`` is exactly 0 (zero terminal SNR).  Host only, so callers raise before anything is launched."""
+    ac = getattr(scheduler, 'alphas_cumprod', None)
+    if ac is None or getattr(scheduler, 'prediction_type', None) != 'epsilon':
+        return
+    ts = scheduler.timesteps
+    for t in (ts.tolist() if isinstance(ts, torch.Tensor) else ts):
+        if float(t) == int(t) and float(ac[int(t)]) == 0.0:
+            raise _zero_snr_epsilon_error(int(t))
+
+
+def check_snr_gamma(gamma):
+    """``snr_gamma=``: None (no weighting) or a finite float > 0."""
+    if gamma is None:
+        return None
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma) or gamma <= 0:
+        raise ValueError(f'snr_gamma must be None or a finite number > 0, got {gamma!r}')
+    return float(gamma)
+
+
+def min_snr_weights(alphas_cumprod: torch.Tensor, gamma: float, prediction_type: str) -> torch.Tensor:
+    """The Min-SNR-gamma loss weight of every timestep (Hang et al., arXiv:2303.09556) as a float64 table, from the
+    ``alphas_cumprod`` table taken to float64: with SNR = abar / (1 - abar), min(SNR, gamma) / SNR for ``epsilon`` (1 where
+    SNR = 0, the limit) and min(SNR, gamma) / (SNR + 1) for ``v_prediction``."""
+    gamma = check_snr_gamma(gamma)
+    if gamma is None:
+        raise ValueError('min_snr_weights needs a gamma')
+    ac = alphas_cumprod.to(torch.float64)
+    snr = ac / (1.0 - ac)
+    capped = torch.clamp(snr, max=gamma)
+    if prediction_type == 'v_prediction':
+        return capped / (snr + 1.0)
+    if prediction_type == 'epsilon':
+        return torch.where(snr > 0, capped / torch.where(snr > 0, snr, torch.ones_like(snr)), torch.ones_like(snr))
+    raise ValueError(f'Min-SNR weighting is defined for epsilon and v_prediction, got {prediction_type!r}')

@@ -19,9 +19,10 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..sampling import LatentSampler, resolve_sampler
+from ..sampling import LatentSampler, check_guidance_rescale, rescale_noise_cfg, resolve_sampler
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
-from .schedulers import check_inference_scheduler, resolve_inference_scheduler
+from .schedulers import (check_inference_scheduler, check_snr_gamma, check_timestep_spacing, check_zero_snr_grid,
+                         min_snr_weights, resolve_inference_scheduler, with_timestep_spacing)
 from .unet import UNetHIP
 from .vae import DiagonalGaussian
 
@@ -67,8 +68,17 @@ class StableDiffusion(ComposerModel):
                  precomputed_latents: bool = False,
                  encode_latents_in_fp16: bool = False,
                  fsdp: bool = False,
-                 prediction_type: Optional[str] = None):
+                 prediction_type: Optional[str] = None,
+                 snr_gamma: Optional[float] = None,
+                 guidance_rescale: float = 0.0):
+        """``snr_gamma``: None, or the gamma of Min-SNR loss weighting (Hang et al., arXiv:2303.09556): every sample's
+        squared error and gradient are weighted by its timestep's entry of ``schedulers.min_snr_weights`` in the fused loss
+        launch (``ops.mse_loss_w``); ``loss()`` then reports the weighted loss.  ``guidance_rescale``: the default of
+        ``generate(guidance_rescale=None)``, hence of ``eval_forward`` and the image metrics and loggers built on it."""
         super().__init__()
+        self.snr_gamma = _check_loss_options(snr_gamma, loss_fn)
+        self.guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._snr_tables = {}
         self.unet = unet
         self.vae = vae
         self.noise_scheduler = noise_scheduler
@@ -130,6 +140,7 @@ class StableDiffusion(ComposerModel):
                 self.vae._fsdp_wrap = False
             self.unet._fsdp_wrap = True
         self._pending = None
+        self._pending_t = None
 
     # ------------------------------------------------------------------------------------------
     def _text_states(self, input_ids):
@@ -228,7 +239,18 @@ class StableDiffusion(ComposerModel):
         pred = pred8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2)
         target = target8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2) if v_pred else noise
         self._pending = (pred8, target8, B * H * W)
+        # the timesteps of the pending forward, kept only for the Min-SNR weighted loss
+        self._pending_t = t if self.snr_gamma is not None else None
         return pred, target, timesteps
+
+    def snr_weight_table(self, device):
+        """The Min-SNR weight of every training timestep as an fp32 table on ``device``: built once on the host in float64
+        (``schedulers.min_snr_weights``) from ``noise_scheduler.alphas_cumprod``, cached per device like ``device_tables``."""
+        key = str(device)
+        if key not in self._snr_tables:
+            w = min_snr_weights(self.noise_scheduler.alphas_cumprod, self.snr_gamma, self.prediction_type)
+            self._snr_tables[key] = w.to(torch.float32).to(device).contiguous()
+        return self._snr_tables[key]
 
     def loss(self, outputs, batch, weight: float = 1.0):
         """MSE between U-Net output and target (reference :185-187) - fused loss + gradient kernel.
@@ -240,7 +262,14 @@ class StableDiffusion(ComposerModel):
         if self.loss_fn is F.mse_loss:
             dpred = torch.empty(npix, 8, device=pred8.device, dtype=torch.bfloat16)
             lossbuf = torch.zeros(1, device=pred8.device, dtype=torch.float32)
-            ops.mse_loss(pred8, target8, dpred, lossbuf, unet._scratch, npix, 2.0 * weight / (4.0 * npix), 1.0, 0)
+            if self.snr_gamma is not None:   # the same fused launch with the timestep's Min-SNR weight per sample
+                t = self._pending_t
+                if t is None:
+                    raise RuntimeError('snr_gamma was set after forward(): loss() has no timesteps to weight by')
+                ops.mse_loss_w(pred8, target8, dpred, lossbuf, unet._scratch, npix, 4, npix // t.numel(), t,
+                               self.snr_weight_table(pred8.device), 2.0 * weight / (4.0 * npix), 1.0, 0)
+            else:
+                ops.mse_loss(pred8, target8, dpred, lossbuf, unet._scratch, npix, 2.0 * weight / (4.0 * npix), 1.0, 0)
             self._dpred = dpred
             anchor = torch.zeros((), device=pred8.device, requires_grad=True)
             return _HIPBackward.apply(anchor, lossbuf[0], self)
@@ -324,6 +353,7 @@ class StableDiffusion(ComposerModel):
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None, height: Optional[int] = None,
                  width: Optional[int] = None, num_inference_steps: int = 50, guidance_scale: float = 3.0,
                  num_images_per_prompt: int = 1, seed: Optional[int] = None, progress_bar: bool = True,
+                 guidance_rescale: Optional[float] = None, timestep_spacing: Optional[str] = None,
                  sampler: Optional[str] = None, inference_scheduler=None, init_image: Optional[torch.Tensor] = None,
                  strength: float = 0.8, mask: Optional[torch.Tensor] = None):
         """DDIM sampling with classifier-free guidance on the HIP U-Net forward (reference :260-382).
@@ -342,7 +372,14 @@ class StableDiffusion(ComposerModel):
         ``mask`` (inpainting, needs ``init_image``): [H, W], [1, 1, H, W] or [B, 1, H, W] in [0, 1], 1 = repaint, 0 = keep,
         fractions blend; after every step the latent outside the mask is replaced by ``z0`` re-noised to the level of the
         next timestep (the 4-channel scheme of diffusers' ``StableDiffusionInpaintPipeline``).  Kept areas come back through
-        the VAE round trip: there is no pixel-space composite after decoding.  Every ``sampler=`` route takes them."""
+        the VAE round trip: there is no pixel-space composite after decoding.  Every ``sampler=`` route takes them.
+
+        ``guidance_rescale`` (phi in [0, 1]; default the model's ``guidance_rescale``): under guidance the guided prediction
+        is scaled per sample to phi std(cond) / std(guided) + 1 - phi times itself (Lin et al., arXiv:2305.08891; diffusers'
+        ``rescale_noise_cfg``).  ``timestep_spacing``: ``'leading'`` or ``'trailing'`` for this call; default the
+        scheduler's own.  Both apply on every ``sampler=`` route, with either solver, with ``init_image`` and ``mask``.  An
+        epsilon-prediction scheduler on a zero-terminal-SNR table raises ``ValueError`` if the grid visits the last
+        timestep.  All of it is checked before anything is launched."""
         sampler = resolve_sampler(sampler)
         check_inference_scheduler(inference_scheduler)
         _check_prompt_given(prompt, tokenized_prompts, prompt_embeds)
@@ -352,6 +389,9 @@ class StableDiffusion(ComposerModel):
         height, width, start_index = _check_init_image(
             init_image, strength, mask, height, width, num_inference_steps,
             _prompt_batch(prompt, tokenized_prompts, prompt_embeds) * num_images_per_prompt)
+        scheduler, guidance_rescale = _resolve_sampling_options(
+            inference_scheduler, self.inference_scheduler, guidance_rescale, self.guidance_rescale, timestep_spacing,
+            num_inference_steps)
         device = self.unet.device_
         rng = torch.Generator(device=device)
         if seed:
@@ -379,14 +419,14 @@ class StableDiffusion(ComposerModel):
                 mask_px = mask.to(device, torch.float32).reshape(-1, height, width).expand(batch_size, -1, -1).contiguous()
         latents = torch.randn((batch_size, self.unet.config.in_channels, height // vae_scale, width // vae_scale),
                               device=device, generator=rng)
-        scheduler = resolve_inference_scheduler(inference_scheduler, self.inference_scheduler)
         scheduler.set_timesteps(num_inference_steps)
         latents = latents * scheduler.init_noise_sigma
         if sampler != 'torch':
             partial = {} if z0 is None else dict(known=z0, start_index=start_index, mask_px=mask_px)
             latents = LatentSampler(self.unet, scheduler).sample(
                 latents, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
-                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar, **partial)
+                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar,
+                guidance_rescale=guidance_rescale, **partial)
         else:   # the reference's loop, the scheduler step in torch ops
             timesteps = scheduler.timesteps
             if z0 is not None:   # the same method in torch ops: start from the noised image, run the tail of the schedule
@@ -403,7 +443,7 @@ class StableDiffusion(ComposerModel):
                 pred = self.unet(lin, t, encoder_hidden_states=text_embeddings).sample
                 if do_cfg:
                     pu, pt = pred.chunk(2)
-                    pred = pu + guidance_scale * (pt - pu)
+                    pred = rescale_noise_cfg(pu + guidance_scale * (pt - pu), pt, guidance_rescale)
                 latents = scheduler.step(pred, t, latents, generator=rng)['prev_sample']
                 if mask_px is not None:   # outside the mask: the known latent at the noise level of the next timestep
                     kn = scheduler.add_noise(z0, noise, timesteps[i + 1:i + 2]) if i + 1 < len(timesteps) else z0
@@ -446,6 +486,29 @@ class StableDiffusion(ComposerModel):
         bs_embed, seq_len, _ = prompt_embeds.shape
         prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1)
         return prompt_embeds.view(bs_embed * num_images_per_prompt, seq_len, -1)
+
+
+def _check_loss_options(snr_gamma, loss_fn):
+    """``StableDiffusion(snr_gamma=..., loss_fn=...)``: the checked gamma.  The weighting lives in the fused MSE launch, so a
+    user ``loss_fn`` together with it is refused rather than silently unweighted."""
+    snr_gamma = check_snr_gamma(snr_gamma)
+    if snr_gamma is not None and loss_fn is not F.mse_loss:
+        raise ValueError('snr_gamma weights the fused MSE loss: it cannot be combined with a custom loss_fn')
+    return snr_gamma
+
+
+def _resolve_sampling_options(inference_scheduler, own_scheduler, guidance_rescale, default_rescale, timestep_spacing,
+                              num_inference_steps):
+    """``generate(guidance_rescale=..., timestep_spacing=..., inference_scheduler=...)`` on the host: (the scheduler of this
+    call with its grid set, phi).  ``ValueError`` for phi outside [0, 1], an unknown spacing, and an epsilon-prediction
+    scheduler whose grid visits a timestep of zero SNR."""
+    phi = check_guidance_rescale(default_rescale if guidance_rescale is None else guidance_rescale)
+    if timestep_spacing is not None:
+        check_timestep_spacing(timestep_spacing)
+    scheduler = with_timestep_spacing(resolve_inference_scheduler(inference_scheduler, own_scheduler), timestep_spacing)
+    scheduler.set_timesteps(num_inference_steps)
+    check_zero_snr_grid(scheduler)
+    return scheduler, phi
 
 
 def _check_prompt_lenths(prompt, negative_prompt):

@@ -645,9 +645,39 @@ def clip_score(img, txt, scores, state):
               _vec(scores, B, 'scores'), _vec(state, 2, 'state'), _stream())
 
 
-def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copies=1):
+def _rescale_operands(fn, factor, HW, npix):
+    """``factor=`` / ``HW=`` of the four step wrappers (guidance rescale): the sample's pixel count, checked."""
+    if HW is None or int(HW) < 1 or npix % int(HW):
+        raise ValueError(f'{fn}: factor needs HW, the pixel count of one sample, dividing npix = {npix}; got {HW}')
+    if factor.dtype != F32 or not factor.is_cuda or not factor.is_contiguous() or factor.numel() != npix // int(HW):
+        raise ValueError(f'{fn}: factor must be a contiguous fp32 [{npix // int(HW)}] device tensor')
+    return int(HW)
+
+
+def guidance_rescale(pred, coef, factor, *, phi, HW, C, g_index):
+    """The statistics pass of guidance rescale (``da_guidance_rescale``): factor[b] = phi std(pt) / std(m) + 1 - phi per
+    sample, with m = pu + g (pt - pu) and g = coef[g_index] read on the device (3: the ``sampler_step`` rows, 5: the
+    ``sampler_step_ms`` rows).  pred fp32 [2 npix, 8] (both guidance halves); factor fp32 [npix / HW]; phi in [0, 1]."""
+    C, HW, g_index, phi = int(C), int(HW), int(g_index), float(phi)
+    if not 1 <= C <= 8 or HW < 1 or not 0.0 <= phi <= 1.0:
+        raise ValueError(f'guidance_rescale: C = {C} (1..8), HW = {HW} (>= 1), phi = {phi} (in [0, 1])')
+    if pred.dim() != 2 or pred.shape[1] != 8 or pred.dtype != F32 or not pred.is_cuda or not pred.is_contiguous() \
+            or pred.shape[0] < 2 or pred.shape[0] % (2 * HW) or pred.data_ptr() % 16:
+        raise ValueError(f'guidance_rescale: pred must be a contiguous fp32 [2 B * {HW}, 8] device tensor, 16-byte aligned')
+    npix = pred.shape[0] // 2
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() not in (4, 8) \
+            or coef.data_ptr() % 16 or not 0 <= g_index < coef.numel():
+        raise ValueError('guidance_rescale: coef must be 4 or 8 contiguous fp32 on the device, 16-byte aligned, g_index inside')
+    _rescale_operands('guidance_rescale', factor, HW, npix)
+    _lib.call('da_guidance_rescale', pred.data_ptr(), coef.data_ptr(), g_index, phi, factor.data_ptr(), npix, HW, C,
+              _stream())
+
+
+def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copies=1, factor=None, HW=None):
     """One sampling step after the U-Net call (``da_sampler_step``): guidance, the scheduler update with the device
-    coefficients ``coef`` = {cx, cm, cn, guidance} and the next U-Net input.
+    coefficients ``coef`` = {cx, cm, cn, guidance} and the next U-Net input.  With ``factor`` (fp32 [npix / HW], what
+    ``guidance_rescale`` wrote; ``HW`` the pixel count of one sample) the guided prediction of sample b is multiplied by
+    factor[b] first (``da_sampler_step_rs``); the other three step wrappers take the same two keywords.
 
     pred fp32 [(2 if cfg else 1) * npix, 8]; x / x_out fp32 [npix, 8] (x_out may be x); noise None or fp32 NCHW
     [B, C, H, W] with B * H * W = npix; xt_out None or bf16 [copies * npix, 8]."""
@@ -662,7 +692,7 @@ def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copie
             raise ValueError(f'sampler_step: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
     if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 4 or coef.data_ptr() % 16:
         raise ValueError('sampler_step: coef must be 4 contiguous fp32 on the device, 16-byte aligned')
-    HW = npix
+    HW_arg, HW = HW, npix
     if noise is not None:
         if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
                 or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
@@ -671,12 +701,19 @@ def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copie
     if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
                                or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
         raise ValueError(f'sampler_step: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    if factor is not None:
+        if _rescale_operands('sampler_step', factor, HW_arg, npix) != HW and noise is not None:
+            raise ValueError(f'sampler_step: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
+        _lib.call('da_sampler_step_rs', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
+                  coef.data_ptr(), factor.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None,
+                  npix, int(HW_arg), C, int(cfg), copies, _stream())
+        return
     _lib.call('da_sampler_step', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
               coef.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg),
               copies, _stream())
 
 
-def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1):
+def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1, factor=None, HW=None):
     """One sampling step of a two-step scheduler after the U-Net call (``da_sampler_step_ms``): guidance, the data
     prediction, the update with the previous step's data prediction and the next U-Net input.  ``coef`` = {ax, am, kx, k0,
     k1, guidance, 0, 0} on the device (``DPMSolverMultistepScheduler.step_coefficients_ms``).
@@ -699,6 +736,12 @@ def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1
     if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
                                or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
         raise ValueError(f'sampler_step_ms: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    if factor is not None:
+        HW = _rescale_operands('sampler_step_ms', factor, HW, npix)
+        _lib.call('da_sampler_step_ms_rs', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
+                  factor.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None, npix, HW, C,
+                  int(cfg), copies, _stream())
+        return
     _lib.call('da_sampler_step_ms', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(), x_out.data_ptr(),
               xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
 
@@ -712,7 +755,8 @@ def _blend_operands(fn, known8, eps8, mask, npix):
         raise ValueError(f'{fn}: mask must be a contiguous fp32 [{npix}] device tensor, 16-byte aligned')
 
 
-def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, noise=None, *, C, cfg, copies=1):
+def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, noise=None, *, C, cfg, copies=1, factor=None,
+                       HW=None):
     """``sampler_step`` for a masked sample (``da_sampler_step_blend``): with v what ``sampler_step`` stores and m the pixel's
     mask value, x_out = m v + (1 - m) (bA known8 + bS eps8).  ``coef`` = {cx, cm, cn, guidance, bA, bS, 0, 0} on the device.
 
@@ -729,7 +773,7 @@ def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, no
     _blend_operands('sampler_step_blend', known8, eps8, mask, npix)
     if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
         raise ValueError('sampler_step_blend: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
-    HW = npix
+    HW_arg, HW = HW, npix
     if noise is not None:
         if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
                 or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
@@ -739,12 +783,20 @@ def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, no
     if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
                                or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
         raise ValueError(f'sampler_step_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    if factor is not None:
+        if _rescale_operands('sampler_step_blend', factor, HW_arg, npix) != HW and noise is not None:
+            raise ValueError(f'sampler_step_blend: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
+        _lib.call('da_sampler_step_blend_rs', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
+                  coef.data_ptr(), known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), factor.data_ptr(), x_out.data_ptr(),
+                  xt_out.data_ptr() if xt_out is not None else None, npix, int(HW_arg), C, int(cfg), copies, _stream())
+        return
     _lib.call('da_sampler_step_blend', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
               coef.data_ptr(), known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
               xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg), copies, _stream())
 
 
-def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out=None, *, C, cfg, copies=1):
+def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out=None, *, C, cfg, copies=1, factor=None,
+                          HW=None):
     """``sampler_step_ms`` for a masked sample (``da_sampler_step_ms_blend``): the same blend after the two-step update;
     ``hist`` receives the unblended data prediction.  ``coef`` = {ax, am, kx, k0, k1, guidance, bA, bS} on the device."""
     C, copies, cfg = int(C), int(copies), bool(cfg)
@@ -765,6 +817,12 @@ def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out
     if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
                                or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
         raise ValueError(f'sampler_step_ms_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    if factor is not None:
+        HW = _rescale_operands('sampler_step_ms_blend', factor, HW, npix)
+        _lib.call('da_sampler_step_ms_blend_rs', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
+                  known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), factor.data_ptr(), x_out.data_ptr(),
+                  xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg), copies, _stream())
+        return
     _lib.call('da_sampler_step_ms_blend', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
               known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
               xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
@@ -850,6 +908,26 @@ def mse_loss_c(pred, target, dpred, loss, scratch, total_pix, C, grad_coef, weig
         raise ValueError('mse_loss_c: loss fp32 on device, 1 <= C <= 8')
     _lib.call('da_mse_loss_c', pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), loss.data_ptr(),
               _f32buf(scratch, 1024), total_pix, int(C), float(grad_coef), float(weight), int(accumulate), _stream())
+
+
+def mse_loss_w(pred, target, dpred, loss, scratch, total_pix, C, HW, t, wtab, grad_coef, weight, accumulate):
+    """``mse_loss_c`` with a weight per sample (``da_mse_loss_w``): sample b = pixel // HW weighs wtab[t[b]] in the loss and
+    in dpred.  t int64 [total_pix / HW] and wtab fp32 [T] on the device; a timestep outside the table is clamped into it."""
+    for z, dt in ((pred, F32), (target, F32), (dpred, BF16)):
+        if z.dtype != dt or not z.is_cuda or not z.is_contiguous() or z.numel() != total_pix * 8 or z.data_ptr() % 16:
+            raise ValueError('mse_loss_w: pred / target fp32 and dpred bf16, contiguous [total_pix, 8] on device')
+    if loss.dtype != F32 or not loss.is_cuda or not 1 <= int(C) <= 8:
+        raise ValueError('mse_loss_w: loss fp32 on device, 1 <= C <= 8')
+    HW = int(HW)
+    if HW < 1 or total_pix < 1 or total_pix % HW:
+        raise ValueError(f'mse_loss_w: total_pix = {total_pix} must be a positive multiple of HW = {HW}')
+    if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != total_pix // HW:
+        raise ValueError(f'mse_loss_w: t must be a contiguous int64 [{total_pix // HW}] device tensor')
+    if wtab.dtype != F32 or not wtab.is_cuda or not wtab.is_contiguous() or wtab.dim() != 1 or wtab.numel() < 1:
+        raise ValueError('mse_loss_w: wtab must be a contiguous fp32 [T] device tensor')
+    _lib.call('da_mse_loss_w', pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), loss.data_ptr(), _f32buf(scratch, 1024),
+              total_pix, int(C), HW, t.data_ptr(), wtab.data_ptr(), int(wtab.numel()), float(grad_coef), float(weight),
+              int(accumulate), _stream())
 
 
 def adamw(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale, ema=None, ema_smoothing=0.0):

@@ -15,6 +15,9 @@ A sample may start from an image (``sample(known=...)``: image-to-image): ``ops.
 the level of timestep ``start_index`` in one launch and only the tail of the schedule runs.  With a pixel mask
 (``mask_px``: inpainting) every step is the blended launch (``ops.sampler_step_blend`` / ``ops.sampler_step_ms_blend``),
 which replaces the state outside the mask by the known sample re-noised to the level of the next timestep.
+With ``guidance_rescale`` = phi > 0 under guidance (Lin et al., arXiv:2305.08891) one more launch per step
+(``ops.guidance_rescale``: per sample phi std(pt) / std(m) + 1 - phi) precedes the step, whose ``_rs`` form multiplies the
+guided prediction by it.
 Nothing in the loop reads the device back.  ``graph=True`` replays one captured step (walk + ``sampler_step``) per
 denoising step, as ``graph_step.GraphedMicrobatch`` does for a training microbatch; the host then issues two 16-byte-class
 copies (the step's timestep and coefficient rows) and a replay.
@@ -45,15 +48,37 @@ def resolve_sampler(sampler: Optional[str]) -> str:
     return name
 
 
+def check_guidance_rescale(phi) -> float:
+    """``guidance_rescale=`` of the factory, ``generate()`` and ``LatentSampler.sample``: a number in [0, 1], else
+    ``ValueError``.  Host only."""
+    if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= float(phi) <= 1.0:
+        raise ValueError(f'guidance_rescale must be a number in [0, 1], got {phi!r}')
+    return float(phi)
+
+
+def rescale_noise_cfg(guided: torch.Tensor, cond: torch.Tensor, guidance_rescale: float) -> torch.Tensor:
+    """diffusers' ``rescale_noise_cfg`` in torch ops, what the ``sampler='torch'`` loop applies: the guided prediction
+    [B, C, H, W] scaled per sample back to the conditional prediction's standard deviation, blended by ``guidance_rescale``.
+    0 returns ``guided`` itself."""
+    if guidance_rescale == 0.0:
+        return guided
+    dims = list(range(1, guided.dim()))
+    rescaled = guided * (cond.std(dim=dims, keepdim=True) / guided.std(dim=dims, keepdim=True))
+    return guidance_rescale * rescaled + (1 - guidance_rescale) * guided
+
+
 class GraphedSamplerStep:
     """One captured denoising step for one signature: forward-only walk + ``sampler_step`` over static buffers."""
 
     def __init__(self, unet, rows: int, B: int, HW, C: int, cfg: bool, t_dtype, ctx: torch.Tensor, kv: dict,
-                 multistep: bool = False, blend: bool = False):
+                 multistep: bool = False, blend: bool = False, phi: float = 0.0):
         dev = unet.device_
         H, W = HW
         self.unet, self.rows, self.HW, self.C, self.cfg, self.multistep = unet, rows, (H, W), C, cfg, multistep
         self.blend = blend
+        # guidance rescale: phi is a launch argument of the captured statistics pass, so it is part of the cache key
+        self.phi = phi
+        self.factor = torch.ones(B, device=dev, dtype=torch.float32) if phi > 0.0 else None
         npix = B * H * W
         self.x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
         self.xt = torch.zeros(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
@@ -82,16 +107,17 @@ class GraphedSamplerStep:
 
     def _body(self):
         pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.HW, kv=self.kv, record=False)
+        rs = _rescale_pass(pred, self.coef, self.factor, self.phi, self.HW[0] * self.HW[1], self.C, self.multistep)
         if self.blend:
             _blended_step(pred, self.x, self.hist, self.coef, self.known8, self.eps8, self.mask, self.xt, None, C=self.C,
-                          cfg=self.cfg, copies=2 if self.cfg else 1)
+                          cfg=self.cfg, copies=2 if self.cfg else 1, **rs)
             return
         if self.multistep:
             ops.sampler_step_ms(pred, self.x, self.hist, self.coef, self.x, self.xt, C=self.C, cfg=self.cfg,
-                                copies=2 if self.cfg else 1)
+                                copies=2 if self.cfg else 1, **rs)
             return
         ops.sampler_step(pred, self.x, self.coef, self.x, self.xt, None, C=self.C, cfg=self.cfg,
-                         copies=2 if self.cfg else 1)
+                         copies=2 if self.cfg else 1, **rs)
 
     def load(self, ctx, kv):
         self.ctx.copy_(ctx, non_blocking=True)
@@ -102,6 +128,15 @@ class GraphedSamplerStep:
         self.t.copy_(t_row, non_blocking=True)
         self.coef.copy_(coef_row, non_blocking=True)
         self.graph.replay()
+
+
+def _rescale_pass(pred, coef, factor, phi, HW, C, multistep):
+    """The statistics launch of guidance rescale, when there is one (``factor`` is the sampler's buffer, None without
+    rescale): the keywords the step launch takes after it."""
+    if factor is None:
+        return {}
+    ops.guidance_rescale(pred, coef, factor, phi=phi, HW=HW, C=C, g_index=5 if multistep else 3)
+    return dict(factor=factor, HW=HW)
 
 
 def _blended_step(pred, x, hist, coef, known8, eps8, mask, xt, noise, **kw):
@@ -139,7 +174,8 @@ class LatentSampler:
     def sample(self, latents: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor] = None, *,
                num_inference_steps: int, guidance_scale: float, graph: bool = False,
                progress_bar: bool = False, known: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-               start_index: int = 0, mask_px: Optional[torch.Tensor] = None) -> torch.Tensor:
+               start_index: int = 0, mask_px: Optional[torch.Tensor] = None,
+               guidance_rescale: float = 0.0) -> torch.Tensor:
         """latents: the initial noise [B, C, H, W] (already scaled by ``init_noise_sigma``); cond / uncond: [B, L, D] text
         states.  Classifier-free guidance runs iff ``guidance_scale > 1.0`` (``uncond`` is then required).  Returns the
         denoised [B, C, H, W] fp32 (latent models: before the 1 / 0.18215 rescale).
@@ -149,8 +185,11 @@ class LatentSampler:
         ``start_index`` and steps ``start_index .. n - 1`` run; discrete-time schedulers only.  ``mask_px`` (inpainting,
         needs ``known``): fp32 [B, f H, f W] in [0, 1] at f x f pixels per state pixel (f a power of two in 1..16; 8 for the
         latent models), 1 = repaint, 0 = keep; its f x f box mean weighs every step's blend with the re-noised known
-        sample.  Every check of these raises ``ValueError`` before anything is launched."""
+        sample.  ``guidance_rescale`` (phi in [0, 1]): under guidance and with phi > 0 every step scales the guided
+        prediction per sample by phi std(pt) / std(m) + 1 - phi; otherwise the launches are the ones without it.  Every
+        check of these raises ``ValueError`` before anything is launched."""
         unet, sch = self.unet, self.scheduler
+        phi = check_guidance_rescale(guidance_rescale)
         if known is None:
             if mask_px is not None:
                 raise ValueError('mask_px needs known: the sample whose unmasked part is kept')
@@ -174,6 +213,7 @@ class LatentSampler:
         if cfg and uncond is None:
             raise ValueError('guidance_scale > 1 needs the unconditional text states')
         rows, npix = (2 * B if cfg else B), B * H * W
+        phi = phi if cfg else 0.0
         sch.set_timesteps(num_inference_steps)
         ts = sch.timesteps
         ts = ts.tolist() if isinstance(ts, torch.Tensor) else [float(t) for t in ts]
@@ -218,8 +258,8 @@ class LatentSampler:
         g = None
         if graph and not stochastic and ops.PROFILE is None:   # the SDE needs a fresh draw per step: eager
             key = (rows, H, W, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1]) + (('multistep',) if multistep else ()) \
-                + (('blend',) if blend else ())
-            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep, blend)
+                + (('blend',) if blend else ()) + (('rescale', phi) if phi > 0.0 else ())
+            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep, blend, phi)
             g.load(ctx, kv)
             x, xt, hist = g.x, g.xt, g.hist
             known8, eps8, mask = g.known8, g.eps8, g.mask
@@ -232,6 +272,7 @@ class LatentSampler:
             known8 = torch.empty(npix, 8, device=dev, dtype=torch.float32) if blend else None
             eps8 = torch.empty(npix, 8, device=dev, dtype=torch.float32) if blend else None
             mask = torch.empty(npix, device=dev, dtype=torch.float32) if blend else None
+        factor = torch.empty(B, device=dev, dtype=torch.float32) if phi > 0.0 and g is None else None
         lat = latents.to(dev, torch.float32).contiguous()
         if known is None:
             # NCHW -> NHWC-8 of the initial noise (and its bf16 copies) by the step kernel itself: 0 x + 0 m + 1 z
@@ -248,14 +289,16 @@ class LatentSampler:
                 g.step(t_tab[i], coef_tab[i])
                 continue
             pred = unet.forward_features(xt, t_tab[i], ctx, rows, (H, W), kv=kv, record=False)
+            rs = _rescale_pass(pred, coef_tab[i], factor, phi, H * W, C, multistep)
             if blend:   # discrete time: no noise draw
                 _blended_step(pred, x, hist, coef_tab[i], known8, eps8, mask, xt if i + 1 < n else None, None, C=C, cfg=cfg,
-                              copies=copies)
+                              copies=copies, **rs)
                 continue
             if multistep:
-                ops.sampler_step_ms(pred, x, hist, coef_tab[i], x, xt if i + 1 < n else None, C=C, cfg=cfg, copies=copies)
+                ops.sampler_step_ms(pred, x, hist, coef_tab[i], x, xt if i + 1 < n else None, C=C, cfg=cfg, copies=copies,
+                                    **rs)
                 continue
             # the Euler-Maruyama draw: global generator, after the U-Net call, the shape step() draws (randn_like(sample))
             noise = torch.randn((B, C, H, W), device=dev) if stochastic else None
-            ops.sampler_step(pred, x, coef_tab[i], x, xt if i + 1 < n else None, noise, C=C, cfg=cfg, copies=copies)
+            ops.sampler_step(pred, x, coef_tab[i], x, xt if i + 1 < n else None, noise, C=C, cfg=cfg, copies=copies, **rs)
         return x.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2).contiguous()

@@ -307,6 +307,32 @@ int da_sampler_step_blend(const float* pred, const float* x, const float* noise,
 int da_sampler_step_ms_blend(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
                              const float* eps8, const float* mask, float* x_out, void* xt_out, long npix, int HW, int C,
                              int cfg, int copies, da_stream_t stream);
+/* Guidance rescale (Lin et al., arXiv:2305.08891, section 3.4; diffusers' rescale_noise_cfg): the statistics pass.  With pt
+ * the conditional half of pred (rows [npix, 2 npix)), pu the unconditional half, g = coef[g_index] read on the device (3 for
+ * the da_sampler_step rows, 5 for the da_sampler_step_ms rows) and m = pu + g (pt - pu), per sample b over its C valid
+ * channels and HW pixels:
+ *   factor[b] = phi * std(pt) / std(m) + (1 - phi)          exactly 1 when std(m) == 0
+ *   pred   fp32 [2 npix][8];  factor fp32 [npix / HW];  phi in [0, 1], a launch argument (not device data).
+ * Both standard deviations have the same count, so the Bessel factor cancels.  One workgroup per sample; m and the sums are
+ * formed in fp64 from the fp32 operands, on data shifted by the sample's first value, in a fixed order: every call gives the same bits, and |mean| >> std costs no
+ * accuracy.  Channels C..7 of pred are not used, whatever they hold.  DA_ERR_SHAPE for npix <= 0 or no multiple of HW, C
+ * outside 1..8, g_index outside 0..7, phi outside [0, 1], a NULL pointer, or pred / coef not 16-byte aligned. */
+int da_guidance_rescale(const float* pred, const float* coef, int g_index, float phi, float* factor, long npix, int HW,
+                        int C, da_stream_t stream);
+/* The four step forms with guidance rescale: everything as in the entry without _rs, except that m is multiplied by
+ * factor[pixel / HW] (fp32 [npix / HW], what da_guidance_rescale wrote) before the scheduler update, so HW must be the pixel
+ * count of one sample also where there is no noise draw.  A factor of exactly 1 gives the bits of the plain entry.
+ * DA_ERR_SHAPE as for the plain entry, and for a NULL factor. */
+int da_sampler_step_rs(const float* pred, const float* x, const float* noise, const float* coef, const float* factor,
+                       float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+int da_sampler_step_ms_rs(const float* pred, const float* x, float* hist, const float* coef, const float* factor,
+                          float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+int da_sampler_step_blend_rs(const float* pred, const float* x, const float* noise, const float* coef, const float* known8,
+                             const float* eps8, const float* mask, const float* factor, float* x_out, void* xt_out,
+                             long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+int da_sampler_step_ms_blend_rs(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
+                                const float* eps8, const float* mask, const float* factor, float* x_out, void* xt_out,
+                                long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
 /* The start of a sample that begins from an image (image-to-image, inpainting), one launch:
  *   known   fp32 NCHW [B][C][H][W], the clean sample (latent models: already scaled); noise the same shape;
  *   mask_px NULL, or fp32 [B][f H][f W], the mask at f x f pixels per state pixel, f a power of two in 1..16;
@@ -367,6 +393,18 @@ int da_mse_loss(const float* pred, const float* target, void* dpred, float* loss
  * gradient.  pred, target, dpred 16-byte aligned; DA_ERR_SHAPE for C outside 1..8. */
 int da_mse_loss_c(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix,
                   int C, float grad_coef, float weight, int accumulate, da_stream_t stream);
+/* the da_mse_loss_c contract with a weight per sample, looked up by the sample's timestep (Min-SNR-gamma weighting, Hang et
+ * al., arXiv:2303.09556): with b = pixel / HW and w_b = wtab[t[b]],
+ *   dpred = grad_coef * w_b * (pred - target)  (bf16, exactly 0 in channels C..7),
+ *   loss[0] (+)= weight * (1 / (C * total_pix)) * sum_b w_b sum (pred - target)^2.
+ * t (int64 [total_pix / HW]) and wtab (fp32 [T]) are DEVICE pointers, so the launch can sit in a captured graph.  A timestep
+ * outside [0, T) is clamped into the table, never read outside it.  Same two launches and fixed summation order as
+ * da_mse_loss_c (two calls give the same bits; scratch >= 1024 floats); with a table of ones dpred and the loss are
+ * da_mse_loss_c's bits.  DA_ERR_SHAPE for total_pix no multiple of HW, HW <= 0, T <= 0, a NULL t or wtab, C outside 1..8, or
+ * a misaligned pred / target / dpred. */
+int da_mse_loss_w(const float* pred, const float* target, void* dpred, float* loss, float* scratch, long total_pix, int C,
+                  int HW, const long long* t, const float* wtab, int T, float grad_coef, float weight, int accumulate,
+                  da_stream_t stream);
 
 /* torch.optim.AdamW step (train.py:33; SD-2-base-256.yaml:55-58) on flat fp32 master/moment buffers, gradient
  * pre-scaled by grad_scale; also writes the bf16 compute shadow.  If ema != NULL the exponential moving average of

@@ -3,7 +3,7 @@ step in torch ops), ``'hip'`` (``sampling.LatentSampler``) and ``'graph'`` (the 
 one JSON line.
 
   python tools/sample_bench.py [--batches 1,4,16] [--steps 20] [--px 256] [--guidance 3.0] [--seconds 6] [--model NAME]
-                                [--scheduler ddim|dpm++2m] [--inpaint]
+                                [--scheduler ddim|dpm++2m] [--inpaint] [--guidance-rescale PHI]
 
 SD-2-base U-Net, random init, precomputed text embeddings (no VAE, no text encoder: the loop alone), latents of
 ``px / 8``.  Per batch size B (2 B U-Net rows with guidance):
@@ -20,6 +20,9 @@ interleaved calls of one session.
 ``--inpaint`` adds ``inpaint`` to the same rounds: the ``'hip'`` mode as a masked sample (``sample(known=, mask_px=)``, a
 half-plane mask, ``start_index=0`` so that it runs the same ``--steps`` steps), i.e. one ``sampler_init`` launch and the
 blended step launch in place of the plain one.  ``ms_per_step_vs_hip`` is its median call over the unmasked ``'hip'`` one.
+``--guidance-rescale PHI`` (PHI in (0, 1], needs ``--guidance`` > 1) adds ``rescale`` to the same rounds: the ``'hip'`` mode
+with ``sample(guidance_rescale=PHI)``, i.e. one statistics launch per step and the rescaled step launch in place of the plain
+one.  ``ms_per_step_vs_hip`` is its median call over the plain ``'hip'`` one and ``ms_per_step_over_hip`` the difference.
 """
 import argparse
 import json
@@ -45,7 +48,10 @@ def main():
     ap.add_argument('--model', default='stabilityai/stable-diffusion-2-base')
     ap.add_argument('--scheduler', default='ddim', choices=('ddim', 'dpm++2m'))
     ap.add_argument('--inpaint', action='store_true')
+    ap.add_argument('--guidance-rescale', type=float, default=0.0)
     a = ap.parse_args()
+    if a.guidance_rescale and not (0.0 < a.guidance_rescale <= 1.0 and a.guidance > 1.0):
+        raise SystemExit('sample_bench: --guidance-rescale takes PHI in (0, 1] and needs --guidance > 1')
 
     import torch
     from diffusion_amd.models.models import stable_diffusion_2
@@ -58,7 +64,8 @@ def main():
                                inference_scheduler=a.scheduler)
     unet, sch = model.unet, model.inference_scheduler
     sampler = LatentSampler(unet, sch)
-    modes = MODES + (('ddim_hip',) if a.scheduler != 'ddim' else ()) + (('inpaint',) if a.inpaint else ())
+    modes = MODES + (('ddim_hip',) if a.scheduler != 'ddim' else ()) + (('inpaint',) if a.inpaint else ()) \
+        + (('rescale',) if a.guidance_rescale else ())
     ddim_sampler = LatentSampler(unet, make_inference_scheduler('ddim', like=sch))
     S, D = a.px // 8, unet.cfg.cross_attention_dim
     cfg = a.guidance > 1.0
@@ -80,6 +87,9 @@ def main():
         if mode == 'inpaint':
             return sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance, known=known,
                                   start_index=0, mask_px=mask_px)
+        if mode == 'rescale':
+            return sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance,
+                                  guidance_rescale=a.guidance_rescale)
         if mode == 'torch':
             return torch_loop(lat, txt, unc)
         if mode == 'ddim_hip':
@@ -87,7 +97,7 @@ def main():
         return sampler.sample(lat, txt, unc, num_inference_steps=a.steps, guidance_scale=a.guidance, graph=mode == 'graph')
 
     res = {'bench': 'sample', 'model': a.model, 'scheduler': a.scheduler, 'px': a.px, 'steps': a.steps, 'guidance': a.guidance,
-           'seconds_per_batch': a.seconds, 'batches': []}
+           'guidance_rescale': a.guidance_rescale, 'seconds_per_batch': a.seconds, 'batches': []}
     for B in (int(b) for b in a.batches.split(',')):
         g = torch.Generator().manual_seed(100 + B)
         lat = torch.randn(B, unet.cfg.in_channels, S, S, generator=g).to(dev)
@@ -130,6 +140,11 @@ def main():
         if 'inpaint' in modes:
             row['inpaint']['ms_per_step_vs_hip'] = round(statistics.median(times['inpaint']) /
                                                          statistics.median(times['hip']), 4)
+        if 'rescale' in modes:
+            row['rescale']['ms_per_step_vs_hip'] = round(statistics.median(times['rescale']) /
+                                                         statistics.median(times['hip']), 4)
+            row['rescale']['ms_per_step_over_hip'] = round((statistics.median(times['rescale']) -
+                                                            statistics.median(times['hip'])) * 1e3 / a.steps, 4)
         for m in ('hip', 'graph'):
             row[m]['speedup_vs_torch'] = round(statistics.median(times['torch']) / statistics.median(times[m]), 3)
         res['batches'].append(row)
