@@ -10,8 +10,11 @@
 // read where torch.randn left it (NCHW, as da_add_noise reads eps).
 // A sample that starts from an image (image-to-image, inpainting) adds da_sampler_init, the start of a partial schedule in
 // one launch, and the blended forms of both steps: outside a per-pixel mask the state is replaced by the known sample
-// re-noised to the level of the next timestep.  The unmasked kernels are the BLEND = false instantiations of the same
-// bodies.
+// re-noised to the level of the next timestep.
+// The step is the product {first-order, two-step} x {plain, blended} x {plain, rescaled}: eight C entries, and behind them
+// ONE kernel body (sampler_step_kernel<MS, BLEND, RS>) and ONE host path (step<MS, BLEND, RS>: the argument rules and the
+// launch).  What a form does not use is an empty operand struct and code under `if constexpr`, so the plain instantiations
+// are the kernels they were before the other forms existed.
 #include "common.hpp"
 #include "diffusion_amd.h"
 
@@ -46,86 +49,43 @@ struct Rescale {
 template <>
 struct Rescale<false> {};  // the plain kernels: the operand list and the arithmetic they always had
 
-// every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
-// BLEND: coef is the row widened to eight floats, {cx, cm, cn, guidance, bA, bS, 0, 0}
-template <bool BLEND, bool RS = false>
-__global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
-    sampler_step_kernel(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, bf16* xt_out,
-                        long npix, int HW, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
-  const f32x4 k = *reinterpret_cast<const f32x4*>(coef);
-  const float cx = k[0], cm = k[1], cn = k[2], g = k[3];
-  float bA = 0.f, bS = 0.f;
-  if constexpr (BLEND) {
-    const f32x4 kb = *reinterpret_cast<const f32x4*>(coef + 4);
-    bA = kb[0], bS = kb[1];
-  }
-  GRID_STRIDE(i, npix) {
-    const f32x4 x0 = *reinterpret_cast<const f32x4*>(x + i * 8), x1 = *reinterpret_cast<const f32x4*>(x + i * 8 + 4);
-    const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
-    f32x4 q0 = p0, q1 = p1;
-    if (cfg) {  // uniform: rows [npix, 2 npix) are the conditional half
-      q0 = *reinterpret_cast<const f32x4*>(pred + (npix + i) * 8);
-      q1 = *reinterpret_cast<const f32x4*>(pred + (npix + i) * 8 + 4);
-    }
-    float kn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mk = 1.f;
-    if constexpr (BLEND) {
-      const f32x4 n0 = *reinterpret_cast<const f32x4*>(bl.known8 + i * 8),
-                  n1 = *reinterpret_cast<const f32x4*>(bl.known8 + i * 8 + 4);
-      const f32x4 e0 = *reinterpret_cast<const f32x4*>(bl.eps8 + i * 8), e1 = *reinterpret_cast<const f32x4*>(bl.eps8 + i * 8 + 4);
-      mk = bl.mask[i];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) kn[c] = bA * (c < 4 ? n0[c & 3] : n1[c & 3]) + bS * (c < 4 ? e0[c & 3] : e1[c & 3]);
-    }
-    const long b = i / HW;
-    const int pix = (int)(i - b * HW);
-    float fac = 1.f;
-    if constexpr (RS) fac = rs.factor[i / rs.hw];
-    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c < C) {
-        const float xv = c < 4 ? x0[c & 3] : x1[c & 3], pu = c < 4 ? p0[c & 3] : p1[c & 3];
-        float m = pu;
-        if (cfg) {
-          const float pt = c < 4 ? q0[c & 3] : q1[c & 3];
-          m = pu + g * (pt - pu);
-        }
-        if constexpr (RS) m *= fac;
-        float v = cx * xv + cm * m;
-        if (noise) v += cn * noise[(b * C + c) * HW + pix];
-        if constexpr (BLEND) v = mk * v + (1.f - mk) * kn[c];
-        o[c] = v;
-      }
-    }
-    *reinterpret_cast<f32x4*>(x_out + i * 8) = f32x4{o[0], o[1], o[2], o[3]};
-    *reinterpret_cast<f32x4*>(x_out + i * 8 + 4) = f32x4{o[4], o[5], o[6], o[7]};
-    if (xt_out) {
-      bf16x8 t;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) t[c] = f2bf(o[c]);
-      st8(xt_out + i * 8, t);
-      if (copies == 2) st8(xt_out + (npix + i) * 8, t);
-    }
-  }
-}
+// The operand only one order of the step has.  First order: the noise draw (NCHW, NULL without one) and HW, the pixel count
+// of one sample, which indexes it.  Two-step: the previous step's data prediction, read iff k1 != 0 and then overwritten.
+template <bool MS>
+struct Form {
+  const float* noise;
+  int HW;
+};
+template <>
+struct Form<true> {
+  float* hist;
+};
 
-// The two-step (DPM-Solver++ 2M) form of the same launch: one operand wider.  The host reduces a step to five coefficients
-// (DPMSolverMultistepScheduler.step_coefficients_ms) and the kernel carries the previous step's data prediction in `hist`:
+// The step, every form of it.  First order (MS = false), coef = {cx, cm, cn, guidance} and, BLEND, {bA, bS, 0, 0} after it:
+//   m     = cfg ? pu + g (pt - pu) : p
+//   v     = cx x + cm m (+ cn z)
+// Two-step (MS: DPM-Solver++ 2M, one operand wider), coef = {ax, am, kx, k0, k1, guidance, bA, bS}: the host reduces a step
+// to five coefficients (DPMSolverMultistepScheduler.step_coefficients_ms) and the kernel carries the previous step's data
+// prediction in `hist`:
 //   m     = cfg ? pu + g (pt - pu) : p
 //   d     = ax x + am m                         the data prediction x0 of this step
 //   v     = kx x + k0 d (+ k1 hist)             k1 == 0 (a first-order step): hist is not read, it may hold anything
-//   hist  = d,  x_out = v,  xt = bf16(v)        channels C..7 of all three exactly 0
+//   hist  = d
 // k1 comes from device memory like the rest, so one captured launch serves first- and second-order steps alike.
+// Every form: RS multiplies m by the sample's factor first, BLEND replaces v by m v + (1 - m) kn last, and
+//   x_out = v,  xt = bf16(v)                    channels C..7 of x_out, xt and hist exactly 0
 // every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
-// BLEND: coef = {ax, am, kx, k0, k1, guidance, bA, bS}
-template <bool BLEND, bool RS = false>
+template <bool MS, bool BLEND, bool RS>
 __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
-    sampler_step_ms_kernel(const float* pred, const float* x, float* hist, const float* coef, float* x_out, bf16* xt_out,
-                           long npix, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
-  const f32x4 ka = *reinterpret_cast<const f32x4*>(coef), kb = *reinterpret_cast<const f32x4*>(coef + 4);
-  const float ax = ka[0], am = ka[1], kx = ka[2], k0 = ka[3], k1 = kb[0], g = kb[1];
-  const float bA = kb[2], bS = kb[3];  // the row's two free slots; read by the blended form only
-  const bool second = k1 != 0.0f;  // uniform across the launch
+    sampler_step_kernel(const float* pred, const float* x, Form<MS> fm, const float* coef, float* x_out, bf16* xt_out,
+                        long npix, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
+  const f32x4 ka = *reinterpret_cast<const f32x4*>(coef);
+  f32x4 kb = {0, 0, 0, 0};  // the second half of the row: the first-order form has (and reads) one only when blended
+  if constexpr (MS || BLEND) kb = *reinterpret_cast<const f32x4*>(coef + 4);
+  const float c0 = ka[0], c1 = ka[1];  // {cx, cm} or {ax, am}
+  const float cn = ka[2], kx = ka[2], k0 = ka[3], k1 = kb[0];
+  const float g = MS ? kb[1] : ka[3], bA = MS ? kb[2] : kb[0], bS = MS ? kb[3] : kb[1];
+  const bool second = MS && k1 != 0.0f;  // uniform across the launch
   GRID_STRIDE(i, npix) {
     const f32x4 x0 = *reinterpret_cast<const f32x4*>(x + i * 8), x1 = *reinterpret_cast<const f32x4*>(x + i * 8 + 4);
     const f32x4 p0 = *reinterpret_cast<const f32x4*>(pred + i * 8), p1 = *reinterpret_cast<const f32x4*>(pred + i * 8 + 4);
@@ -135,9 +95,11 @@ __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
       q1 = *reinterpret_cast<const f32x4*>(pred + (npix + i) * 8 + 4);
     }
     f32x4 h0 = {0, 0, 0, 0}, h1 = {0, 0, 0, 0};
-    if (second) {
-      h0 = *reinterpret_cast<const f32x4*>(hist + i * 8);
-      h1 = *reinterpret_cast<const f32x4*>(hist + i * 8 + 4);
+    if constexpr (MS) {
+      if (second) {
+        h0 = *reinterpret_cast<const f32x4*>(fm.hist + i * 8);
+        h1 = *reinterpret_cast<const f32x4*>(fm.hist + i * 8 + 4);
+      }
     }
     float kn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mk = 1.f;
     if constexpr (BLEND) {
@@ -147,6 +109,12 @@ __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
       mk = bl.mask[i];
 #pragma unroll
       for (int c = 0; c < 8; ++c) kn[c] = bA * (c < 4 ? n0[c & 3] : n1[c & 3]) + bS * (c < 4 ? e0[c & 3] : e1[c & 3]);
+    }
+    long b = 0;
+    int pix = 0;
+    if constexpr (!MS) {  // where the pixel's noise draw is
+      b = i / fm.HW;
+      pix = (int)(i - b * fm.HW);
     }
     float fac = 1.f;
     if constexpr (RS) fac = rs.factor[i / rs.hw];
@@ -161,16 +129,23 @@ __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
           m = pu + g * (pt - pu);
         }
         if constexpr (RS) m *= fac;
-        const float dv = ax * xv + am * m;
-        float v = kx * xv + k0 * dv;
-        if (second) v += k1 * (c < 4 ? h0[c & 3] : h1[c & 3]);
+        const float dv = c0 * xv + c1 * m;  // first order: the update itself; two-step: the data prediction
+        float v = dv;
+        if constexpr (MS) {
+          v = kx * xv + k0 * dv;
+          if (second) v += k1 * (c < 4 ? h0[c & 3] : h1[c & 3]);
+        } else {
+          if (fm.noise) v += cn * fm.noise[(b * C + c) * fm.HW + pix];
+        }
         if constexpr (BLEND) v = mk * v + (1.f - mk) * kn[c];  // the history keeps the unblended data prediction
-        d[c] = dv;
+        if constexpr (MS) d[c] = dv;
         o[c] = v;
       }
     }
-    *reinterpret_cast<f32x4*>(hist + i * 8) = f32x4{d[0], d[1], d[2], d[3]};
-    *reinterpret_cast<f32x4*>(hist + i * 8 + 4) = f32x4{d[4], d[5], d[6], d[7]};
+    if constexpr (MS) {
+      *reinterpret_cast<f32x4*>(fm.hist + i * 8) = f32x4{d[0], d[1], d[2], d[3]};
+      *reinterpret_cast<f32x4*>(fm.hist + i * 8 + 4) = f32x4{d[4], d[5], d[6], d[7]};
+    }
     *reinterpret_cast<f32x4*>(x_out + i * 8) = f32x4{o[0], o[1], o[2], o[3]};
     *reinterpret_cast<f32x4*>(x_out + i * 8 + 4) = f32x4{o[4], o[5], o[6], o[7]};
     if (xt_out) {
@@ -293,36 +268,90 @@ __global__ void __launch_bounds__(GR_BLOCK)
   }
 }
 
-template <bool BLEND, bool RS>
-int launch_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out, void* xt_out,
-                long npix, int HW, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs, hipStream_t s) {
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL((sampler_step_kernel<BLEND, RS>), dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef,
-                     x_out, (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, bl, rs);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-template <bool BLEND, bool RS>
-int launch_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out, void* xt_out, long npix,
-                   int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs, hipStream_t s) {
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL((sampler_step_ms_kernel<BLEND, RS>), dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
-                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, bl, rs);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+// one work item per pixel: ceil(npix / 256) blocks of 256, capped (the kernels stride over the rest)
+unsigned pixel_grid(long npix) {
+  const long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
+  return (unsigned)(blocks > 16384 ? 16384 : blocks);
 }
 
-// the argument rules every step entry shares; `extra` ORs the form's own pointers, `need` is false when one of them is NULL
-bool step_args_ok(const float* pred, const float* x, const float* coef, float* x_out, void* xt_out, long npix, int HW, int C,
-                  int copies, uintptr_t extra, bool need) {
-  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return false;
-  if (!pred || !x || !coef || !x_out || !need) return false;
-  return !((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)coef | (uintptr_t)x_out | (uintptr_t)xt_out | extra) & 15));
+// What a step entry was called with: the operands every form has, then the ones a form may have (NULL where it has none).
+struct StepArgs {
+  const float *pred, *x, *coef;
+  float* x_out;
+  void* xt_out;
+  long npix;
+  int HW, C, cfg, copies;
+  hipStream_t s;
+  const float* noise = nullptr;  // first order, optional
+  float* hist = nullptr;         // two-step
+  const float *known8 = nullptr, *eps8 = nullptr, *mask = nullptr;  // BLEND
+  const float* factor = nullptr;                                    // RS
+};
+
+// The argument rules of every step entry, each stated once, and the launch.
+template <bool MS, bool BLEND, bool RS>
+int step(const StepArgs& a) {
+  // shapes; the two-step forms check HW like the rest, though only their RS forms read it
+  if (a.npix <= 0 || a.HW <= 0 || (a.npix % a.HW) || a.C < 1 || a.C > 8 || (a.copies != 1 && a.copies != 2))
+    return DA_ERR_SHAPE;
+  // required: the common operands and the form's own; noise and xt_out are optional
+  if (!a.pred || !a.x || !a.coef || !a.x_out) return DA_ERR_SHAPE;
+  if (MS && !a.hist) return DA_ERR_SHAPE;
+  if (BLEND && (!a.known8 || !a.eps8 || !a.mask)) return DA_ERR_SHAPE;
+  if (RS && !a.factor) return DA_ERR_SHAPE;
+  // alignment: 16 bytes for every pointer given (the optional ones included), 4 for factor
+  const uintptr_t ptrs = (uintptr_t)a.pred | (uintptr_t)a.x | (uintptr_t)a.coef | (uintptr_t)a.x_out | (uintptr_t)a.xt_out |
+                         (uintptr_t)a.noise | (uintptr_t)a.hist | (uintptr_t)a.known8 | (uintptr_t)a.eps8 | (uintptr_t)a.mask;
+  if ((ptrs & 15) || ((uintptr_t)a.factor & 3)) return DA_ERR_SHAPE;
+  Form<MS> fm;
+  if constexpr (MS) fm = {a.hist};
+  else fm = {a.noise, a.HW};
+  Blend<BLEND> bl;
+  if constexpr (BLEND) bl = {a.known8, a.eps8, a.mask};
+  Rescale<RS> rs;
+  if constexpr (RS) rs = {a.factor, a.HW};
+  hipLaunchKernelGGL((sampler_step_kernel<MS, BLEND, RS>), dim3(pixel_grid(a.npix)), dim3(SMP_BLOCK), 0, a.s, a.pred, a.x,
+                     fm, a.coef, a.x_out, (bf16*)a.xt_out, a.npix, a.C, a.cfg ? 1 : 0, a.copies, bl, rs);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
 }
 
 }  // namespace
+
+// ---- the eight step entries: the call's operands into a StepArgs, then step<MS, BLEND, RS>
+extern "C" int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out,
+                               void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.noise = noise;
+  return step<false, false, false>(a);
+}
+
+extern "C" int da_sampler_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out,
+                                  void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.hist = hist;
+  return step<true, false, false>(a);
+}
+
+extern "C" int da_sampler_step_blend(const float* pred, const float* x, const float* noise, const float* coef,
+                                     const float* known8, const float* eps8, const float* mask, float* x_out, void* xt_out,
+                                     long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.noise = noise, a.known8 = known8, a.eps8 = eps8, a.mask = mask;
+  return step<false, true, false>(a);
+}
+
+extern "C" int da_sampler_step_ms_blend(const float* pred, const float* x, float* hist, const float* coef,
+                                        const float* known8, const float* eps8, const float* mask, float* x_out,
+                                        void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.hist = hist, a.known8 = known8, a.eps8 = eps8, a.mask = mask;
+  return step<true, true, false>(a);
+}
 
 extern "C" int da_guidance_rescale(const float* pred, const float* coef, int g_index, float phi, float* factor, long npix,
                                    int HW, int C, hipStream_t s) {
@@ -342,22 +371,18 @@ extern "C" int da_sampler_step_rs(const float* pred, const float* x, const float
                                   const float* factor, float* x_out, void* xt_out, long npix, int HW, int C, int cfg,
                                   int copies, hipStream_t s) {
   DA_CLEAR_ERR();
-  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies, (uintptr_t)noise, factor != nullptr) ||
-      ((uintptr_t)factor & 3))
-    return DA_ERR_SHAPE;
-  return launch_step<false, true>(pred, x, noise, coef, x_out, xt_out, npix, HW, C, cfg, copies, Blend<false>{},
-                                  Rescale<true>{factor, HW}, s);
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.noise = noise, a.factor = factor;
+  return step<false, false, true>(a);
 }
 
 extern "C" int da_sampler_step_ms_rs(const float* pred, const float* x, float* hist, const float* coef, const float* factor,
                                      float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
                                      hipStream_t s) {
   DA_CLEAR_ERR();
-  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies, (uintptr_t)hist, hist && factor) ||
-      ((uintptr_t)factor & 3))
-    return DA_ERR_SHAPE;
-  return launch_step_ms<false, true>(pred, x, hist, coef, x_out, xt_out, npix, C, cfg, copies, Blend<false>{},
-                                     Rescale<true>{factor, HW}, s);
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.hist = hist, a.factor = factor;
+  return step<true, false, true>(a);
 }
 
 extern "C" int da_sampler_step_blend_rs(const float* pred, const float* x, const float* noise, const float* coef,
@@ -365,13 +390,9 @@ extern "C" int da_sampler_step_blend_rs(const float* pred, const float* x, const
                                         float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
                                         hipStream_t s) {
   DA_CLEAR_ERR();
-  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies,
-                    (uintptr_t)noise | (uintptr_t)known8 | (uintptr_t)eps8 | (uintptr_t)mask,
-                    known8 && eps8 && mask && factor) ||
-      ((uintptr_t)factor & 3))
-    return DA_ERR_SHAPE;
-  return launch_step<true, true>(pred, x, noise, coef, x_out, xt_out, npix, HW, C, cfg, copies,
-                                 Blend<true>{known8, eps8, mask}, Rescale<true>{factor, HW}, s);
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.noise = noise, a.known8 = known8, a.eps8 = eps8, a.mask = mask, a.factor = factor;
+  return step<false, true, true>(a);
 }
 
 extern "C" int da_sampler_step_ms_blend_rs(const float* pred, const float* x, float* hist, const float* coef,
@@ -379,77 +400,9 @@ extern "C" int da_sampler_step_ms_blend_rs(const float* pred, const float* x, fl
                                            float* x_out, void* xt_out, long npix, int HW, int C, int cfg, int copies,
                                            hipStream_t s) {
   DA_CLEAR_ERR();
-  if (!step_args_ok(pred, x, coef, x_out, xt_out, npix, HW, C, copies,
-                    (uintptr_t)hist | (uintptr_t)known8 | (uintptr_t)eps8 | (uintptr_t)mask,
-                    hist && known8 && eps8 && mask && factor) ||
-      ((uintptr_t)factor & 3))
-    return DA_ERR_SHAPE;
-  return launch_step_ms<true, true>(pred, x, hist, coef, x_out, xt_out, npix, C, cfg, copies,
-                                    Blend<true>{known8, eps8, mask}, Rescale<true>{factor, HW}, s);
-}
-
-extern "C" int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out,
-                               void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return DA_ERR_SHAPE;
-  if (!pred || !x || !coef || !x_out) return DA_ERR_SHAPE;
-  if ((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)coef | (uintptr_t)x_out | (uintptr_t)xt_out) & 15))
-    return DA_ERR_SHAPE;
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sampler_step_kernel<false>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef, x_out,
-                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<false>{}, Rescale<false>{});
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-
-extern "C" int da_sampler_step_ms(const float* pred, const float* x, float* hist, const float* coef, float* x_out,
-                                  void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return DA_ERR_SHAPE;
-  if (!pred || !x || !hist || !coef || !x_out) return DA_ERR_SHAPE;
-  if ((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)hist | (uintptr_t)coef | (uintptr_t)x_out | (uintptr_t)xt_out) & 15))
-    return DA_ERR_SHAPE;
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sampler_step_ms_kernel<false>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
-                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<false>{}, Rescale<false>{});
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-
-extern "C" int da_sampler_step_blend(const float* pred, const float* x, const float* noise, const float* coef,
-                                     const float* known8, const float* eps8, const float* mask, float* x_out, void* xt_out,
-                                     long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return DA_ERR_SHAPE;
-  if (!pred || !x || !coef || !known8 || !eps8 || !mask || !x_out) return DA_ERR_SHAPE;
-  if ((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)coef | (uintptr_t)known8 | (uintptr_t)eps8 |
-        (uintptr_t)mask | (uintptr_t)x_out | (uintptr_t)xt_out) & 15))
-    return DA_ERR_SHAPE;
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sampler_step_kernel<true>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, noise, coef, x_out,
-                     (bf16*)xt_out, npix, HW, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask}, Rescale<false>{});
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-
-extern "C" int da_sampler_step_ms_blend(const float* pred, const float* x, float* hist, const float* coef,
-                                        const float* known8, const float* eps8, const float* mask, float* x_out,
-                                        void* xt_out, long npix, int HW, int C, int cfg, int copies, hipStream_t s) {
-  DA_CLEAR_ERR();
-  if (npix <= 0 || HW <= 0 || (npix % HW) || C < 1 || C > 8 || (copies != 1 && copies != 2)) return DA_ERR_SHAPE;
-  if (!pred || !x || !hist || !coef || !known8 || !eps8 || !mask || !x_out) return DA_ERR_SHAPE;
-  if ((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)hist | (uintptr_t)coef | (uintptr_t)known8 | (uintptr_t)eps8 |
-        (uintptr_t)mask | (uintptr_t)x_out | (uintptr_t)xt_out) & 15))
-    return DA_ERR_SHAPE;
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sampler_step_ms_kernel<true>, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, pred, x, hist, coef,
-                     x_out, (bf16*)xt_out, npix, C, cfg ? 1 : 0, copies, Blend<true>{known8, eps8, mask}, Rescale<false>{});
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.hist = hist, a.known8 = known8, a.eps8 = eps8, a.mask = mask, a.factor = factor;
+  return step<true, true, true>(a);
 }
 
 extern "C" int da_sampler_init(const float* known, const float* noise, const float* mask_px, const float* coef,
@@ -465,9 +418,7 @@ extern "C" int da_sampler_init(const float* known, const float* noise, const flo
         (uintptr_t)mask | (uintptr_t)x | (uintptr_t)xt) & 15))
     return DA_ERR_SHAPE;
   const long npix = (long)B * H * W;
-  long blocks = (npix + SMP_BLOCK - 1) / SMP_BLOCK;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sampler_init_kernel, dim3((unsigned)blocks), dim3(SMP_BLOCK), 0, s, known, noise, mask_px, coef, known8,
+  hipLaunchKernelGGL(sampler_init_kernel, dim3(pixel_grid(npix)), dim3(SMP_BLOCK), 0, s, known, noise, mask_px, coef, known8,
                      eps8, mask, x, (bf16*)xt, npix, H, W, C, f, copies);
   DA_CHECK_LAUNCH();
   return DA_OK;

@@ -673,6 +673,51 @@ def guidance_rescale(pred, coef, factor, *, phi, HW, C, g_index):
               _stream())
 
 
+def _sampler_step(ms, blend, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, *, noise=None, hist=None, known8=None,
+                  eps8=None, mask=None):
+    """The four step wrappers behind their signatures: the form is (``ms``: two-step, with ``hist`` and no ``noise``;
+    ``blend``: masked, with ``known8`` / ``eps8`` / ``mask``), the checks are stated once and raise under the wrapper's name,
+    and the call goes to that form's symbol, its ``_rs`` twin when ``factor`` is given."""
+    fn = 'sampler_step' + ('_ms' if ms else '') + ('_blend' if blend else '')
+    C, copies, cfg = int(C), int(copies), bool(cfg)
+    if not 1 <= C <= 8 or copies not in (1, 2):
+        raise ValueError(f'{fn}: C = {C} (1..8), copies = {copies} (1 or 2)')
+    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
+        raise ValueError(f'{fn}: x must be [npix, 8]')
+    npix = x.shape[0]
+    mats = [(pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x')] + ([(hist, npix, 'hist')] if ms else []) \
+        + [(x_out, npix, 'x_out')] + ([(known8, npix, 'known8'), (eps8, npix, 'eps8')] if blend else [])
+    for z, rows, nm in mats:
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
+            raise ValueError(f'{fn}: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
+    if blend and (mask.dtype != F32 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (npix,)
+                  or mask.data_ptr() % 16):
+        raise ValueError(f'{fn}: mask must be a contiguous fp32 [{npix}] device tensor, 16-byte aligned')
+    # hist is written while the others are still being read
+    if ms and hist.data_ptr() in [z.data_ptr() for z in (x, x_out, pred) + ((known8, eps8) if blend else ())]:
+        raise ValueError(f'{fn}: hist must be a buffer of its own')
+    ncoef = 8 if ms or blend else 4
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != ncoef or coef.data_ptr() % 16:
+        raise ValueError(f'{fn}: coef must be {ncoef} contiguous fp32 on the device, 16-byte aligned')
+    HW_arg, HW = HW, npix
+    if noise is not None:
+        if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
+                or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
+            raise ValueError(f'{fn}: noise must be a contiguous fp32 [B, {C}, H, W] device tensor over {npix} pixels')
+        HW = noise.shape[2] * noise.shape[3]
+    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
+                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
+        raise ValueError(f'{fn}: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
+    if factor is not None:
+        if _rescale_operands(fn, factor, HW_arg, npix) != HW and noise is not None:
+            raise ValueError(f'{fn}: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
+        HW = int(HW_arg)
+    ptr = lambda z: z.data_ptr() if z is not None else None  # noqa: E731
+    _lib.call('da_' + fn + ('_rs' if factor is not None else ''), ptr(pred), ptr(x), ptr(hist if ms else noise), ptr(coef),
+              *((ptr(known8), ptr(eps8), ptr(mask)) if blend else ()), *((ptr(factor),) if factor is not None else ()),
+              ptr(x_out), ptr(xt_out), npix, HW, C, int(cfg), copies, _stream())
+
+
 def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copies=1, factor=None, HW=None):
     """One sampling step after the U-Net call (``da_sampler_step``): guidance, the scheduler update with the device
     coefficients ``coef`` = {cx, cm, cn, guidance} and the next U-Net input.  With ``factor`` (fp32 [npix / HW], what
@@ -681,36 +726,7 @@ def sampler_step(pred, x, coef, x_out, xt_out=None, noise=None, *, C, cfg, copie
 
     pred fp32 [(2 if cfg else 1) * npix, 8]; x / x_out fp32 [npix, 8] (x_out may be x); noise None or fp32 NCHW
     [B, C, H, W] with B * H * W = npix; xt_out None or bf16 [copies * npix, 8]."""
-    C, copies, cfg = int(C), int(copies), bool(cfg)
-    if not 1 <= C <= 8 or copies not in (1, 2):
-        raise ValueError(f'sampler_step: C = {C} (1..8), copies = {copies} (1 or 2)')
-    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
-        raise ValueError('sampler_step: x must be [npix, 8]')
-    npix = x.shape[0]
-    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (x_out, npix, 'x_out')):
-        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
-            raise ValueError(f'sampler_step: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
-    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 4 or coef.data_ptr() % 16:
-        raise ValueError('sampler_step: coef must be 4 contiguous fp32 on the device, 16-byte aligned')
-    HW_arg, HW = HW, npix
-    if noise is not None:
-        if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
-                or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
-            raise ValueError(f'sampler_step: noise must be a contiguous fp32 [B, {C}, H, W] device tensor over {npix} pixels')
-        HW = noise.shape[2] * noise.shape[3]
-    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
-                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
-        raise ValueError(f'sampler_step: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
-    if factor is not None:
-        if _rescale_operands('sampler_step', factor, HW_arg, npix) != HW and noise is not None:
-            raise ValueError(f'sampler_step: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
-        _lib.call('da_sampler_step_rs', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
-                  coef.data_ptr(), factor.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None,
-                  npix, int(HW_arg), C, int(cfg), copies, _stream())
-        return
-    _lib.call('da_sampler_step', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
-              coef.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg),
-              copies, _stream())
+    _sampler_step(False, False, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, noise=noise)
 
 
 def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1, factor=None, HW=None):
@@ -720,39 +736,7 @@ def sampler_step_ms(pred, x, hist, coef, x_out, xt_out=None, *, C, cfg, copies=1
 
     pred fp32 [(2 if cfg else 1) * npix, 8]; x / x_out / hist fp32 [npix, 8] (x_out may be x; hist is read iff k1 != 0 and
     then overwritten with this step's data prediction); xt_out None or bf16 [copies * npix, 8]."""
-    C, copies, cfg = int(C), int(copies), bool(cfg)
-    if not 1 <= C <= 8 or copies not in (1, 2):
-        raise ValueError(f'sampler_step_ms: C = {C} (1..8), copies = {copies} (1 or 2)')
-    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
-        raise ValueError('sampler_step_ms: x must be [npix, 8]')
-    npix = x.shape[0]
-    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (hist, npix, 'hist'), (x_out, npix, 'x_out')):
-        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
-            raise ValueError(f'sampler_step_ms: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
-    if hist.data_ptr() in (x.data_ptr(), x_out.data_ptr(), pred.data_ptr()):
-        raise ValueError('sampler_step_ms: hist must be a buffer of its own')
-    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
-        raise ValueError('sampler_step_ms: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
-    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
-                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
-        raise ValueError(f'sampler_step_ms: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
-    if factor is not None:
-        HW = _rescale_operands('sampler_step_ms', factor, HW, npix)
-        _lib.call('da_sampler_step_ms_rs', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
-                  factor.data_ptr(), x_out.data_ptr(), xt_out.data_ptr() if xt_out is not None else None, npix, HW, C,
-                  int(cfg), copies, _stream())
-        return
-    _lib.call('da_sampler_step_ms', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(), x_out.data_ptr(),
-              xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
-
-
-def _blend_operands(fn, known8, eps8, mask, npix):
-    for z, nm in ((known8, 'known8'), (eps8, 'eps8')):
-        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (npix, 8) or z.data_ptr() % 16:
-            raise ValueError(f'{fn}: {nm} must be a contiguous fp32 [{npix}, 8] device tensor, 16-byte aligned')
-    if mask.dtype != F32 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (npix,) \
-            or mask.data_ptr() % 16:
-        raise ValueError(f'{fn}: mask must be a contiguous fp32 [{npix}] device tensor, 16-byte aligned')
+    _sampler_step(True, False, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, hist=hist)
 
 
 def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, noise=None, *, C, cfg, copies=1, factor=None,
@@ -761,71 +745,16 @@ def sampler_step_blend(pred, x, coef, known8, eps8, mask, x_out, xt_out=None, no
     mask value, x_out = m v + (1 - m) (bA known8 + bS eps8).  ``coef`` = {cx, cm, cn, guidance, bA, bS, 0, 0} on the device.
 
     known8 / eps8 fp32 [npix, 8] and mask fp32 [npix] (what ``sampler_init`` writes); the rest as in ``sampler_step``."""
-    C, copies, cfg = int(C), int(copies), bool(cfg)
-    if not 1 <= C <= 8 or copies not in (1, 2):
-        raise ValueError(f'sampler_step_blend: C = {C} (1..8), copies = {copies} (1 or 2)')
-    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
-        raise ValueError('sampler_step_blend: x must be [npix, 8]')
-    npix = x.shape[0]
-    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (x_out, npix, 'x_out')):
-        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
-            raise ValueError(f'sampler_step_blend: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte aligned')
-    _blend_operands('sampler_step_blend', known8, eps8, mask, npix)
-    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
-        raise ValueError('sampler_step_blend: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
-    HW_arg, HW = HW, npix
-    if noise is not None:
-        if noise.dim() != 4 or noise.dtype != F32 or not noise.is_cuda or not noise.is_contiguous() \
-                or noise.shape[1] != C or noise.shape[0] * noise.shape[2] * noise.shape[3] != npix or noise.data_ptr() % 16:
-            raise ValueError(f'sampler_step_blend: noise must be a contiguous fp32 [B, {C}, H, W] device tensor over {npix} '
-                             'pixels')
-        HW = noise.shape[2] * noise.shape[3]
-    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
-                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
-        raise ValueError(f'sampler_step_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
-    if factor is not None:
-        if _rescale_operands('sampler_step_blend', factor, HW_arg, npix) != HW and noise is not None:
-            raise ValueError(f'sampler_step_blend: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
-        _lib.call('da_sampler_step_blend_rs', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
-                  coef.data_ptr(), known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), factor.data_ptr(), x_out.data_ptr(),
-                  xt_out.data_ptr() if xt_out is not None else None, npix, int(HW_arg), C, int(cfg), copies, _stream())
-        return
-    _lib.call('da_sampler_step_blend', pred.data_ptr(), x.data_ptr(), noise.data_ptr() if noise is not None else None,
-              coef.data_ptr(), known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
-              xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg), copies, _stream())
+    _sampler_step(False, True, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, noise=noise, known8=known8, eps8=eps8,
+                  mask=mask)
 
 
 def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out=None, *, C, cfg, copies=1, factor=None,
                           HW=None):
     """``sampler_step_ms`` for a masked sample (``da_sampler_step_ms_blend``): the same blend after the two-step update;
     ``hist`` receives the unblended data prediction.  ``coef`` = {ax, am, kx, k0, k1, guidance, bA, bS} on the device."""
-    C, copies, cfg = int(C), int(copies), bool(cfg)
-    if not 1 <= C <= 8 or copies not in (1, 2):
-        raise ValueError(f'sampler_step_ms_blend: C = {C} (1..8), copies = {copies} (1 or 2)')
-    if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < 1:
-        raise ValueError('sampler_step_ms_blend: x must be [npix, 8]')
-    npix = x.shape[0]
-    for z, rows, nm in ((pred, (2 if cfg else 1) * npix, 'pred'), (x, npix, 'x'), (hist, npix, 'hist'), (x_out, npix, 'x_out')):
-        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or tuple(z.shape) != (rows, 8) or z.data_ptr() % 16:
-            raise ValueError(f'sampler_step_ms_blend: {nm} must be a contiguous fp32 [{rows}, 8] device tensor, 16-byte '
-                             'aligned')
-    _blend_operands('sampler_step_ms_blend', known8, eps8, mask, npix)
-    if hist.data_ptr() in (x.data_ptr(), x_out.data_ptr(), pred.data_ptr(), known8.data_ptr(), eps8.data_ptr()):
-        raise ValueError('sampler_step_ms_blend: hist must be a buffer of its own')
-    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != 8 or coef.data_ptr() % 16:
-        raise ValueError('sampler_step_ms_blend: coef must be 8 contiguous fp32 on the device, 16-byte aligned')
-    if xt_out is not None and (xt_out.dtype != BF16 or not xt_out.is_cuda or not xt_out.is_contiguous()
-                               or tuple(xt_out.shape) != (copies * npix, 8) or xt_out.data_ptr() % 16):
-        raise ValueError(f'sampler_step_ms_blend: xt_out must be a contiguous bf16 [{copies * npix}, 8] device tensor')
-    if factor is not None:
-        HW = _rescale_operands('sampler_step_ms_blend', factor, HW, npix)
-        _lib.call('da_sampler_step_ms_blend_rs', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
-                  known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), factor.data_ptr(), x_out.data_ptr(),
-                  xt_out.data_ptr() if xt_out is not None else None, npix, HW, C, int(cfg), copies, _stream())
-        return
-    _lib.call('da_sampler_step_ms_blend', pred.data_ptr(), x.data_ptr(), hist.data_ptr(), coef.data_ptr(),
-              known8.data_ptr(), eps8.data_ptr(), mask.data_ptr(), x_out.data_ptr(),
-              xt_out.data_ptr() if xt_out is not None else None, npix, npix, C, int(cfg), copies, _stream())
+    _sampler_step(True, True, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, hist=hist, known8=known8, eps8=eps8,
+                  mask=mask)
 
 
 def sampler_init(known, noise, coef, x, xt=None, *, known8=None, eps8=None, mask_px=None, mask=None, copies=1):

@@ -108,16 +108,8 @@ class GraphedSamplerStep:
     def _body(self):
         pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.HW, kv=self.kv, record=False)
         rs = _rescale_pass(pred, self.coef, self.factor, self.phi, self.HW[0] * self.HW[1], self.C, self.multistep)
-        if self.blend:
-            _blended_step(pred, self.x, self.hist, self.coef, self.known8, self.eps8, self.mask, self.xt, None, C=self.C,
-                          cfg=self.cfg, copies=2 if self.cfg else 1, **rs)
-            return
-        if self.multistep:
-            ops.sampler_step_ms(pred, self.x, self.hist, self.coef, self.x, self.xt, C=self.C, cfg=self.cfg,
-                                copies=2 if self.cfg else 1, **rs)
-            return
-        ops.sampler_step(pred, self.x, self.coef, self.x, self.xt, None, C=self.C, cfg=self.cfg,
-                         copies=2 if self.cfg else 1, **rs)
+        _step_launch(pred, self.x, self.hist, self.known8, self.eps8, self.mask, self.xt, self.coef, None, C=self.C,
+                     cfg=self.cfg, copies=2 if self.cfg else 1, **rs)
 
     def load(self, ctx, kv):
         self.ctx.copy_(ctx, non_blocking=True)
@@ -139,12 +131,18 @@ def _rescale_pass(pred, coef, factor, phi, HW, C, multistep):
     return dict(factor=factor, HW=HW)
 
 
-def _blended_step(pred, x, hist, coef, known8, eps8, mask, xt, noise, **kw):
-    """One masked step in place: the two-step form when there is a history buffer, else the first-order one."""
-    if hist is not None:
+def _step_launch(pred, x, hist, known8, eps8, mask, xt, coef, noise, **kw):
+    """The step launch for this sampler state, in place: the two-step form when there is a history buffer, the blended
+    form when there is a mask; ``noise`` is the first-order forms' draw (None without one), ``kw`` the keywords of the step
+    wrappers (``C``, ``cfg``, ``copies`` and what ``_rescale_pass`` returned)."""
+    if mask is not None and hist is not None:
         ops.sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x, xt, **kw)
-    else:
+    elif mask is not None:
         ops.sampler_step_blend(pred, x, coef, known8, eps8, mask, x, xt, noise, **kw)
+    elif hist is not None:
+        ops.sampler_step_ms(pred, x, hist, coef, x, xt, **kw)
+    else:
+        ops.sampler_step(pred, x, coef, x, xt, noise, **kw)
 
 
 class LatentSampler:
@@ -290,15 +288,9 @@ class LatentSampler:
                 continue
             pred = unet.forward_features(xt, t_tab[i], ctx, rows, (H, W), kv=kv, record=False)
             rs = _rescale_pass(pred, coef_tab[i], factor, phi, H * W, C, multistep)
-            if blend:   # discrete time: no noise draw
-                _blended_step(pred, x, hist, coef_tab[i], known8, eps8, mask, xt if i + 1 < n else None, None, C=C, cfg=cfg,
-                              copies=copies, **rs)
-                continue
-            if multistep:
-                ops.sampler_step_ms(pred, x, hist, coef_tab[i], x, xt if i + 1 < n else None, C=C, cfg=cfg, copies=copies,
-                                    **rs)
-                continue
-            # the Euler-Maruyama draw: global generator, after the U-Net call, the shape step() draws (randn_like(sample))
-            noise = torch.randn((B, C, H, W), device=dev) if stochastic else None
-            ops.sampler_step(pred, x, coef_tab[i], x, xt if i + 1 < n else None, noise, C=C, cfg=cfg, copies=copies, **rs)
+            # the Euler-Maruyama draw: global generator, after the U-Net call, the shape step() draws (randn_like(sample));
+            # a masked sample is discrete time: no draw
+            noise = torch.randn((B, C, H, W), device=dev) if stochastic and not blend else None
+            _step_launch(pred, x, hist, known8, eps8, mask, xt if i + 1 < n else None, coef_tab[i], noise, C=C, cfg=cfg,
+                         copies=copies, **rs)
         return x.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2).contiguous()

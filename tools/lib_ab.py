@@ -6,6 +6,7 @@ per cent, so numbers from different gpurun boxes are not comparable).
   python tools/lib_ab.py <old.so> nt [B]               forward / dgrad GEMM (convs, linears with bias + residual, fused GEGLU)
   python tools/lib_ab.py <old.so> gn                   GroupNorm(+SiLU) forward / backward at the U-Net's shapes
   python tools/lib_ab.py <old.so> pw                   the strided-map, noising and loss kernels of pointwise.hip, bit for bit
+  python tools/lib_ab.py <old.so> smp                  the ten entries of sampler.hip (eight steps, init, guidance rescale), bit for bit
 With candidates, each is timed against <old.so>; without, the shipped library is the candidate.
 
 <old.so> is any earlier build, e.g.  git show <rev>:diffusion_amd/csrc/attention.hip > /tmp/a.hip ; hipcc ... -o tools/_ab/old.so
@@ -296,6 +297,145 @@ def run(old, new, what):
         for op, pcts in spread.items():     # with the same build on both sides this is the op's noise
             print(f'pw spread {op:14s}: new slower by at most {max(0.0, -min(pcts)):4.1f} %, largest |difference| '
                   f'{max(abs(v) for v in pcts):4.1f} %', flush=True)
+    elif what == 'smp':
+        # the ten entries of sampler.hip: every output buffer bit for bit at small edge shapes (one line per entry and
+        # size, every operand combination behind it), then bits and time at the two state sizes generate() uses most
+        import itertools
+        bits = lambda t: t.view(torch.int16 if t.dtype == BF else torch.int32)   # noqa: E731  (NaN-proof)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        gen = torch.Generator(device=dev).manual_seed(5)
+        rnd = lambda *shape: torch.randn(*shape, device=dev, generator=gen)   # noqa: E731
+        steps = [(ms, blend, rs) for rs in (0, 1) for blend in (0, 1) for ms in (0, 1)]
+        name = lambda ms, blend, rs: 'da_sampler_step' + '_ms' * ms + '_blend' * blend + '_rs' * rs   # noqa: E731
+
+        def operands(npix, HW, Cc, cfg, k1):
+            """the inputs of one step, shared by both builds; masks hold exact 0, exact 1 and fractions, factor != 1"""
+            B = npix // HW
+            mask = torch.rand(npix, device=dev, generator=gen)
+            mask[0::3], mask[1::3] = 0.0, 1.0
+            return dict(pred=rnd((2 if cfg else 1) * npix, 8), x=rnd(npix, 8), noise=rnd(B, Cc, HW, 1), hist=rnd(npix, 8),
+                        known8=rnd(npix, 8), eps8=rnd(npix, 8), mask=mask,
+                        factor=0.5 + torch.rand(B, device=dev, generator=gen),
+                        coef1=torch.tensor([0.9, 0.1, 0.3, 3.0, 0.8, 0.6, 0.0, 0.0], device=dev),    # cx cm cn g bA bS
+                        coef2=torch.tensor([0.9, -0.4, 0.5, 0.4, k1, 3.0, 0.8, 0.6], device=dev))   # ax am kx k0 k1 g bA bS
+
+        def step_call(ms, blend, rs, ops_, npix, HW, Cc, cfg, copies, noise, o):
+            """o = (x, x_out, hist, xt_out or None): this build's own buffers (x_out is x when in place)"""
+            x, x_out, hist, xt = o
+            args = [ptr(ops_['pred']), ptr(x), ptr(hist) if ms else (ptr(ops_['noise']) if noise else None),
+                    ptr(ops_['coef2'] if ms else ops_['coef1'])]
+            if blend:
+                args += [ptr(ops_['known8']), ptr(ops_['eps8']), ptr(ops_['mask'])]
+            if rs:
+                args += [ptr(ops_['factor'])]
+            return lambda lib: getattr(lib, name(ms, blend, rs))(*args, ptr(x_out), ptr(xt), npix, HW, Cc, cfg, copies, st)
+
+        def step_bufs(ops_, npix, copies, inplace, with_xt, nan_hist):
+            """fresh buffers per build: outputs start from a sentinel, so a stray or a missing store shows too"""
+            out = []
+            for _ in range(2):
+                x = ops_['x'].clone()
+                hist = torch.full_like(ops_['hist'], float('nan')) if nan_hist else ops_['hist'].clone()
+                out.append((x, x if inplace else torch.full_like(x, 7.0), hist,
+                            torch.full((copies * npix, 8), 7.0, device=dev, dtype=BF) if with_xt else None))
+            return out
+
+        def same(oa, ob):
+            return all(torch.equal(bits(p), bits(q)) for p, q in zip(oa, ob) if p is not None)
+
+        ok_all = True
+        for (ms, blend, rs), (npix, HW) in itertools.product(steps, ((1, 1), (255, 85), (257, 257), (260, 130))):
+            n_cases, bad = 0, []
+            # `order`: the noise draw given or NULL (first-order forms); k1 = 0 over a NaN history or k1 != 0 (two-step)
+            for Cc, cfg, copies, with_xt, inplace, order in itertools.product((1, 3, 4, 8), (0, 1), (1, 2), (1, 0), (1, 0), (1, 0)):
+                ops_ = operands(npix, HW, Cc, cfg, k1=0.25 if order else 0.0)
+                ba, bb = step_bufs(ops_, npix, copies, inplace, with_xt, nan_hist=bool(ms and not order))
+                ra = step_call(ms, blend, rs, ops_, npix, HW, Cc, cfg, copies, order, ba)(old)
+                rb = step_call(ms, blend, rs, ops_, npix, HW, Cc, cfg, copies, order, bb)(new)
+                n_cases += 1
+                if ra != 0 or rb != 0 or not same(ba, bb):
+                    bad.append((Cc, cfg, copies, with_xt, inplace, order, ra, rb))
+            ok_all &= not bad
+            print(f'smp {name(ms, blend, rs)[3:]:26s} npix={npix:3d} HW={HW:3d}: {n_cases} cases (C 1/3/4/8, cfg, copies, xt_out / NULL, '
+                  f'in / out of place, {"k1 = 0 over NaN hist / k1 != 0" if ms else "noise / NULL"}): x_out xt_out'
+                  f'{" hist" if ms else ""}  equal bits {not bad}' + (f'  FIRST DIFFERENCES {bad[:4]}' if bad else ''), flush=True)
+        for (B, H, W), f in itertools.product(((1, 1, 1), (3, 5, 17), (1, 1, 257), (2, 10, 13)), (1, 2)):
+            n_cases, bad = 0, []
+            for Cc, copies, with_xt, with_mask, with_k8 in itertools.product((1, 3, 4, 8), (1, 2), (1, 0), (1, 0), (1, 0)):
+                npix = B * H * W
+                known, noise = rnd(B, Cc, H, W), rnd(B, Cc, H, W)
+                mask_px = torch.rand(B, f * H, f * W, device=dev, generator=gen).round_(decimals=1) if with_mask else None
+                coef = torch.tensor([0.8, 0.6, 0.0, 0.0], device=dev)
+                bufs = [[torch.full((npix, 8), 7.0, device=dev) if with_k8 else None, torch.full((npix, 8), 7.0, device=dev) if with_k8 else None,
+                         torch.full((npix,), 7.0, device=dev) if with_mask else None, torch.full((npix, 8), 7.0, device=dev),
+                         torch.full((copies * npix, 8), 7.0, device=dev, dtype=BF) if with_xt else None] for _ in range(2)]
+                rcs = [lib.da_sampler_init(ptr(known), ptr(noise), ptr(mask_px), ptr(coef), *[ptr(t_) for t_ in o], B, H, W, Cc, f,
+                                           copies, st) for lib, o in zip((old, new), bufs)]
+                n_cases += 1
+                if rcs != [0, 0] or not same(*bufs):
+                    bad.append((Cc, copies, with_xt, with_mask, with_k8, rcs))
+            ok_all &= not bad
+            print(f'smp {"sampler_init":26s} B={B} {H}x{W} f={f}: {n_cases} cases (C 1/3/4/8, copies, xt / NULL, mask / NULL, known8 + eps8 / '
+                  f'NULL): known8 eps8 mask x xt  equal bits {not bad}' + (f'  FIRST DIFFERENCES {bad[:4]}' if bad else ''), flush=True)
+        for npix, HW in ((1, 1), (255, 85), (257, 257), (260, 130)):
+            n_cases, bad = 0, []
+            for Cc, g_index in itertools.product((1, 3, 4, 8), (3, 5)):
+                ops_ = operands(npix, HW, Cc, 1, 0.25)
+                fac = [torch.full((npix // HW,), 7.0, device=dev) for _ in range(2)]
+                rcs = [lib.da_guidance_rescale(ptr(ops_['pred']), ptr(ops_['coef2']), g_index, 0.7, ptr(o), npix, HW, Cc, st)
+                       for lib, o in zip((old, new), fac)]
+                n_cases += 1
+                if rcs != [0, 0] or not same(fac[:1], fac[1:]):
+                    bad.append((Cc, g_index, rcs))
+            ok_all &= not bad
+            print(f'smp {"guidance_rescale":26s} npix={npix:3d} HW={HW:3d}: {n_cases} cases (C 1/3/4/8, g_index 3 / 5): factor  '
+                  f'equal bits {not bad}' + (f'  FIRST DIFFERENCES {bad[:4]}' if bad else ''), flush=True)
+
+        # the workload: B = 16 at 32 x 32 and 64 x 64 latents, C = 4, under guidance, in place, as the sampler launches it.
+        # A launch takes microseconds, so launches per window are calibrated as in `pw`; the rows of the four passes are an
+        # entry's samples for its closing "smp spread" line (with the same build on both sides: its noise)
+        spread = {}
+
+        def row(op, label, fa, fb, outs):
+            fa(); fb(); torch.cuda.synchronize()
+            equal = same(*outs)      # after ONE launch each on equal buffers; the timed launches then iterate in place
+            reps = max(5, min(20000, int(30e3 / max(timeit(fa, 20), 1e-3))))
+            ta, tb = ab(fa, fb, reps=reps, rounds=7)
+            pct = 100 * (ta / tb - 1)
+            spread.setdefault(op, []).append(pct)
+            print(f'smp {op:26s} {label:24s}: {ta:8.2f} -> {tb:8.2f} us ({pct:+5.1f} %, {reps} launches / window)  '
+                  f'equal bits {equal}', flush=True)
+            return equal
+
+        for rep, side in itertools.product((1, 2, 3, 4), (32, 64)):
+            B, Cc, HW = 16, 4, side * side
+            npix, label = B * HW, f'B={B} {Cc}x{side}x{side} pass {rep}'
+            ops_ = operands(npix, HW, Cc, 1, 0.25)
+            # contracting rows: thousands of in-place launches stay finite
+            ops_['coef1'] = torch.tensor([0.9, 0.1, 0.0, 3.0, 0.8, 0.6, 0.0, 0.0], device=dev)
+            ops_['coef2'] = torch.tensor([0.5, 0.1, 0.5, 0.3, 0.1, 3.0, 0.8, 0.6], device=dev)
+            for ms, blend, rs in steps:
+                ba, bb = step_bufs(ops_, npix, 2, True, True, False)
+                ca = step_call(ms, blend, rs, ops_, npix, HW, Cc, 1, 2, 0, ba)
+                cb = step_call(ms, blend, rs, ops_, npix, HW, Cc, 1, 2, 0, bb)
+                ok_all &= row(name(ms, blend, rs)[3:], label, lambda: ca(old), lambda: cb(new), (ba, bb))
+            known, noise = rnd(B, Cc, side, side), rnd(B, Cc, side, side)
+            mask_px = torch.rand(B, 8 * side, 8 * side, device=dev, generator=gen).round_()
+            coef = torch.tensor([0.8, 0.6, 0.0, 0.0], device=dev)
+            bufs = [[torch.full((npix, 8), 7.0, device=dev), torch.full((npix, 8), 7.0, device=dev), torch.full((npix,), 7.0, device=dev),
+                     torch.full((npix, 8), 7.0, device=dev), torch.full((2 * npix, 8), 7.0, device=dev, dtype=BF)] for _ in range(2)]
+            init = lambda lib, o: lib.da_sampler_init(ptr(known), ptr(noise), ptr(mask_px), ptr(coef), *[ptr(t_) for t_ in o], B,   # noqa: E731
+                                                      side, side, Cc, 8, 2, st)
+            ok_all &= row('sampler_init', label, lambda: init(old, bufs[0]), lambda: init(new, bufs[1]), bufs)
+            fac = [[torch.full((B,), 7.0, device=dev)] for _ in range(2)]
+            gr = lambda lib, o: lib.da_guidance_rescale(ptr(ops_['pred']), ptr(ops_['coef2']), 5, 0.7, ptr(o[0]), npix, HW, Cc, st)   # noqa: E731
+            ok_all &= row('guidance_rescale', label, lambda: gr(old, fac[0]), lambda: gr(new, fac[1]), fac)
+        for op, pcts in spread.items():     # with the same build on both sides this is the entry's noise
+            print(f'smp spread {op:26s}: new slower by at most {max(0.0, -min(pcts)):4.1f} %, largest |difference| '
+                  f'{max(abs(v) for v in pcts):4.1f} %', flush=True)
+        print(f'smp every comparison equal bits {ok_all}', flush=True)
+        if not ok_all:
+            raise SystemExit(1)
     else:
         raise SystemExit(__doc__)
 
