@@ -9,6 +9,9 @@
 //     MODE 0  GroupNorm forward statistics      (x, x^2)
 //     MODE 1  GroupNorm(+SiLU) backward sums    (dz, dz*xhat),  dz = dy * silu'(z) when SiLU was fused
 //     MODE 2  column sum                         (x, -)           (bias gradients)
+#include <algorithm>
+#include <utility>
+
 #include "common.hpp"
 #include "diffusion_amd.h"
 
@@ -21,30 +24,75 @@ int g_gn_resident_min_slab = 64 * 1024;  // "gn_resident_min_slab": bytes of one
 
 namespace {
 
-struct ChanReduceParams {
+// ---- the pixel walk shared by chan_reduce and gn_apply2: a thread owns 8 consecutive channels (one 16-B vector) and walks
+// pixels.  Channels are split over blockIdx.z in slabs of <= 512 vectors (4096 channels), images over blockIdx.y, pixel
+// chunks of ppc pixels over blockIdx.x; inside a block thread tid takes vector tid % nvec of the slab and the pixels
+// p0 + tid / nvec, + pxt, ... < p1.  walk_geometry (host) sizes pxt / nchunks / ppc and the grid, pixel_walk (device)
+// reads a thread's place off blockIdx.
+struct WalkParams {
   const bf16* X;
-  const bf16* DY;
-  const float* mean_rstd;  // [B][G][2]
-  const float* gamma;
-  const float* beta;
   float* partial;  // [B][nchunks][C][2]
-  long ldx, lddy;
-  int HW, C, G, cpg, nchunks, ppc, pxt, silu;
+  long ldx;
+  int HW, C, G, cpg, nchunks, ppc, pxt, silu;   // the column sums read nothing past this point: one 64-B line of arguments
+  bf16* OUT; long ldo;
+  const float* mean_rstd;  // [B][G][2]
+  const float* gamma; const float* beta;
+  const bf16* DY; long lddy;
+  const float* coef;       // [B][G][2]
+  const bf16* Radd; long ldr;
 };
 
+struct Walk {
+  int vec0, nvec;  // this block's z-slab: first vector, vectors
+  int lvec, vec;   // this thread's vector, in the slab and in the row
+  int pl;          // pixel lane: live when < pxt (a narrower last slab leaves the block's top lanes idle)
+  int b, p0, p1;   // image, pixel range of the chunk
+};
+
+DEVINL Walk pixel_walk(int C, int HW, int ppc) {
+  Walk w;
+  const int tid = threadIdx.x;
+  w.vec0 = blockIdx.z * 512;
+  w.nvec = min(512, (C >> 3) - w.vec0);
+  w.lvec = tid % w.nvec;
+  w.pl = tid / w.nvec;
+  w.vec = w.vec0 + w.lvec;
+  w.b = blockIdx.y;
+  w.p0 = blockIdx.x * ppc;
+  w.p1 = min(HW, w.p0 + ppc);
+  return w;
+}
+
+// Fills p.pxt / p.nchunks / p.ppc for a block of <= `threads` threads (one slab's vectors if those are more) and returns
+// the launch geometry.  nchunks = 0: as many pixel chunks as give >= 4096 workgroups (>= 8 waves per CU) with >= 4 pixels
+// per thread.  Every z-slab uses the same pxt, sized for the widest slab.
+void walk_geometry(WalkParams& p, int B, int threads, int nchunks, dim3& grid, dim3& block) {
+  const int nvec_total = p.C >> 3;
+  const int zsplit = (nvec_total + 511) / 512;
+  const int nvec = nvec_total < 512 ? nvec_total : 512;
+  int pxt = threads / nvec;
+  if (pxt > p.HW) pxt = p.HW;
+  if (pxt < 1) pxt = 1;
+  if (!nchunks) {
+    nchunks = (4096 + B * zsplit - 1) / (B * zsplit);
+    const int maxc = p.HW / (4 * pxt);
+    if (nchunks > maxc) nchunks = maxc;
+    if (nchunks < 1) nchunks = 1;
+  }
+  p.pxt = pxt;
+  p.nchunks = nchunks;
+  p.ppc = (p.HW + nchunks - 1) / nchunks;
+  grid = dim3(nchunks, B, zsplit);
+  block = dim3(nvec * pxt);
+}
+
 template <int MODE>
-__global__ void chan_reduce_kernel(ChanReduceParams p) {
+__global__ void chan_reduce_kernel(WalkParams p) {
   extern __shared__ __attribute__((aligned(16))) float red[];
   const int tid = threadIdx.x;
-  // channels are split over blockIdx.z in slabs of <= 512 vectors (4096 channels)
-  const int vec0 = blockIdx.z * 512;
-  const int nvec = min(512, (p.C >> 3) - vec0);
-  const int Cb = nvec * 8;
-  const int lvec = tid % nvec, pl = tid / nvec;
-  const int vec = vec0 + lvec;
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int p0 = chunk * p.ppc;
-  const int p1 = min(p.HW, p0 + p.ppc);
+  const Walk w = pixel_walk(p.C, p.HW, p.ppc);
+  const int Cb = w.nvec * 8;
+  const int lvec = w.lvec, pl = w.pl, vec = w.vec, b = w.b, chunk = blockIdx.x;
   const bool active = pl < p.pxt;
   float s1[8], s2[8];
 #pragma unroll
@@ -65,7 +113,7 @@ __global__ void chan_reduce_kernel(ChanReduceParams p) {
     }
   }
   if (active) {
-    for (int pix = p0 + pl; pix < p1; pix += p.pxt) {
+    for (int pix = w.p0 + pl; pix < w.p1; pix += p.pxt) {
       const long row = (long)b * p.HW + pix;
       bf16x8 x = ld8(p.X + row * p.ldx + 8 * vec);
       if (MODE == 0) {
@@ -98,7 +146,7 @@ __global__ void chan_reduce_kernel(ChanReduceParams p) {
     }
   }
   __syncthreads();
-  float* out = p.partial + (((long)b * p.nchunks + chunk) * p.C + 8 * vec0) * 2;
+  float* out = p.partial + (((long)b * p.nchunks + chunk) * p.C + 8 * w.vec0) * 2;
   for (int c = tid; c < Cb; c += blockDim.x) {
     float a = 0.f, q = 0.f;
     for (int k = 0; k < p.pxt; ++k) {
@@ -110,23 +158,13 @@ __global__ void chan_reduce_kernel(ChanReduceParams p) {
   }
 }
 
-int launch_chan_reduce(int mode, ChanReduceParams& p, int B, hipStream_t stream) {
-  const int nvec_total = p.C >> 3;
-  if (nvec_total < 1) return DA_ERR_SHAPE;
-  const int zsplit = (nvec_total + 511) / 512;
-  // every z-slab uses the same pxt, sized for the widest slab
-  const int nvec = nvec_total < 512 ? nvec_total : 512;
-  int pxt = 512 / nvec;
-  if (pxt > p.HW) pxt = p.HW;
-  if (pxt < 1) pxt = 1;
-  p.pxt = pxt;
-  p.ppc = (p.HW + p.nchunks - 1) / p.nchunks;
-  const size_t smem = (size_t)pxt * nvec * 8 * 2 * sizeof(float);
-  // the last slab may be narrower: its threads beyond nvec_last*pxt idle via the `active` predicate
-  dim3 grid(p.nchunks, B, zsplit), block(nvec * pxt);
-  if (mode == 0) hipLaunchKernelGGL(chan_reduce_kernel<0>, grid, block, smem, stream, p);
-  else if (mode == 1) hipLaunchKernelGGL(chan_reduce_kernel<1>, grid, block, smem, stream, p);
-  else hipLaunchKernelGGL(chan_reduce_kernel<2>, grid, block, smem, stream, p);
+// the caller's nchunks partial rows per image; LDS holds the block's [pxt][Cb][2] sums
+int launch_chan_reduce(int mode, WalkParams& p, int B, int nchunks, hipStream_t stream) {
+  dim3 grid, block;
+  walk_geometry(p, B, 512, nchunks, grid, block);
+  const size_t smem = (size_t)block.x * 8 * 2 * sizeof(float);
+  const auto kernel = mode == 0 ? chan_reduce_kernel<0> : mode == 1 ? chan_reduce_kernel<1> : chan_reduce_kernel<2>;
+  hipLaunchKernelGGL(kernel, grid, block, smem, stream, p);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -140,7 +178,9 @@ int pick_chunks(int B, int HW) {
   return n;
 }
 
-// ---- GroupNorm forward finalize: partial -> mean/rstd [B][G][2] and per-(b,c) scale/shift [B][C][2]
+// ---- GroupNorm finalize: the per-chunk partials of chan_reduce -> per (image, group) [B][G][2]
+//   forward   (mean, rstd)                               from (sum x, sum x^2)
+//   backward  coef = (mean(gamma*dz), mean(gamma*dz*xhat))   from (sum dz, sum dz*xhat)
 // grid (B, ceil(G / GN_GPB)): a block owns GN_GPB groups of one image (one block per image was 24 us per call at
 // batch 64: 64 blocks, each thread walking up to 10 channels x 32 chunks serially)
 constexpr int GN_GPB = 8;
@@ -162,18 +202,18 @@ DEVINL void chunk_sum2(const float* pp, long stride, int nchunks, float& a, floa
   q = q0 + q1;
 }
 
-__global__ void gn_fwd_finalize_kernel(const float* partial, const float* gamma, const float* beta, float* mean_rstd,
-                                       float* scale_shift, int C, int G, int cpg, int nchunks, int HW, float eps) {
-  extern __shared__ __attribute__((aligned(16))) float sh[];  // [GN_GPB*cpg][2] then [GN_GPB][2]
+template <bool BWD>
+__global__ void gn_finalize_kernel(const float* partial, const float* gamma /* BWD */, float* out, int C, int G, int cpg,
+                                   int nchunks, int HW, float eps /* !BWD */) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];  // [GN_GPB*cpg][2]
   const int b = blockIdx.x;
   const int g0 = blockIdx.y * GN_GPB, ng = min(GN_GPB, G - g0);
   const int c0 = g0 * cpg, nc = ng * cpg;
-  float* gs = sh + 2 * GN_GPB * cpg;
   for (int cl = threadIdx.x; cl < nc; cl += blockDim.x) {
     float a, q;
     chunk_sum2(partial + ((long)b * nchunks * C + c0 + cl) * 2, (long)C * 2, nchunks, a, q);
-    sh[2 * cl] = a;
-    sh[2 * cl + 1] = q;
+    sh[2 * cl] = BWD ? a * gamma[c0 + cl] : a;
+    sh[2 * cl + 1] = BWD ? q * gamma[c0 + cl] : q;
   }
   __syncthreads();
   for (int gl = threadIdx.x; gl < ng; gl += blockDim.x) {
@@ -183,92 +223,36 @@ __global__ void gn_fwd_finalize_kernel(const float* partial, const float* gamma,
       q += sh[2 * (gl * cpg + k) + 1];
     }
     const float n = (float)cpg * (float)HW;
-    float mean = a / n;
-    float var = fmaxf(q / n - mean * mean, 0.f);
-    float rstd = rsqrtf(var + eps);
-    gs[2 * gl] = mean;
-    gs[2 * gl + 1] = rstd;
-    mean_rstd[((long)b * G + g0 + gl) * 2] = mean;
-    mean_rstd[((long)b * G + g0 + gl) * 2 + 1] = rstd;
-  }
-  __syncthreads();
-  for (int cl = threadIdx.x; cl < nc; cl += blockDim.x) {
-    const int gl = cl / cpg, c = c0 + cl;
-    float sc = gs[2 * gl + 1] * gamma[c];
-    scale_shift[((long)b * C + c) * 2] = sc;
-    scale_shift[((long)b * C + c) * 2 + 1] = beta[c] - gs[2 * gl] * sc;
+    float o0 = a / n, o1 = q / n;
+    if (!BWD) {
+      const float var = fmaxf(o1 - o0 * o0, 0.f);
+      o1 = rsqrtf(var + eps);
+    }
+    out[((long)b * G + g0 + gl) * 2] = o0;
+    out[((long)b * G + g0 + gl) * 2 + 1] = o1;
   }
 }
 
-// y = x*scale + shift (+SiLU)
-__global__ void gn_apply_kernel(const bf16* X, long ldx, bf16* Y, long ldy, const float* scale_shift, int HW, int C,
-                                long total_vec, int silu) {
-  const int nvec = C >> 3;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec; i += (long)gridDim.x * blockDim.x) {
-    long row = i / nvec;
-    int vec = (int)(i - row * nvec);
-    int b = (int)(row / HW);
-    bf16x8 x = ld8(X + row * ldx + 8 * vec);
-    const float* ss = scale_shift + ((long)b * C + 8 * vec) * 2;
-    bf16x8 y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float z = bf2f(x[e]) * ss[2 * e] + ss[2 * e + 1];
-      y[e] = f2bf(silu ? silu_f(z) : z);
-    }
-    st8(Y + row * ldy + 8 * vec, y);
-  }
-}
-
-// ---- GroupNorm backward finalize: per (b,g) coefficients (mean(dxhat), mean(dxhat*xhat)); grid as the forward one
-__global__ void gn_bwd_finalize_kernel(const float* partial, const float* gamma, float* coef, int C, int G, int cpg,
-                                       int nchunks, int HW) {
-  extern __shared__ __attribute__((aligned(16))) float sh[];
-  const int b = blockIdx.x;
-  const int g0 = blockIdx.y * GN_GPB, ng = min(GN_GPB, G - g0);
-  const int c0 = g0 * cpg, nc = ng * cpg;
-  for (int cl = threadIdx.x; cl < nc; cl += blockDim.x) {
-    float a, q;
-    chunk_sum2(partial + ((long)b * nchunks * C + c0 + cl) * 2, (long)C * 2, nchunks, a, q);
-    sh[2 * cl] = a * gamma[c0 + cl];
-    sh[2 * cl + 1] = q * gamma[c0 + cl];
-  }
-  __syncthreads();
-  for (int gl = threadIdx.x; gl < ng; gl += blockDim.x) {
-    float a = 0.f, q = 0.f;
-    for (int k = 0; k < cpg; ++k) {
-      a += sh[2 * (gl * cpg + k)];
-      q += sh[2 * (gl * cpg + k) + 1];
-    }
-    const float n = (float)cpg * (float)HW;
-    coef[((long)b * G + g0 + gl) * 2] = a / n;
-    coef[((long)b * G + g0 + gl) * 2 + 1] = q / n;
-  }
+int launch_gn_finalize(bool bwd, const float* partial, const float* gamma, float* out, int B, int C, int G, int nchunks,
+                       int HW, float eps, hipStream_t stream) {
+  const dim3 grid(B, (G + GN_GPB - 1) / GN_GPB);
+  const size_t smem = (size_t)(2 * GN_GPB * (C / G)) * sizeof(float);
+  hipLaunchKernelGGL(bwd ? gn_finalize_kernel<true> : gn_finalize_kernel<false>, grid, dim3(256), smem, stream, partial,
+                     gamma, out, C, G, C / G, nchunks, HW, eps);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
 }
 
 // ---- GroupNorm apply, forward and backward, "channel-stationary": a thread keeps its 8 channels' coefficients
-// in registers and walks pixels (same geometry as chan_reduce), instead of re-deriving per-element group indices
+// in registers and walks pixels (the pixel walk above, as chan_reduce), instead of re-deriving per-element group indices
 // and re-loading statistics for every element.
 //   fwd:  y  = act(x*sc + sh)                      sc = rstd*gamma, sh = beta - mean*sc
 //   bwd:  dx = dz*sc + x*Q + R (+ Radd)            dz = dy*silu'(x*sc+sh) ; Q = -rstd^2*c2 ; R = -rstd*c1 + mean*rstd^2*c2
-struct GnApplyParams {
-  const bf16* X; const bf16* DY; const bf16* Radd; bf16* OUT;
-  const float* mean_rstd; const float* coef; const float* gamma; const float* beta;
-  long ldx, lddy, ldr, ldo;
-  int HW, C, G, cpg, nchunks, ppc, pxt, silu;
-};
-
 template <bool BWD>
-__global__ void gn_apply2_kernel(GnApplyParams p) {
-  const int tid = threadIdx.x;
-  const int vec0 = blockIdx.z * 512;
-  const int nvec = min(512, (p.C >> 3) - vec0);
-  const int lvec = tid % nvec, pl = tid / nvec;
-  if (pl >= p.pxt) return;
-  const int vec = vec0 + lvec;
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int p0 = chunk * p.ppc;
-  const int p1 = min(p.HW, p0 + p.ppc);
+__global__ void gn_apply2_kernel(WalkParams p) {
+  const Walk w = pixel_walk(p.C, p.HW, p.ppc);
+  if (w.pl >= p.pxt) return;
+  const int vec = w.vec, b = w.b;
   float sc[8], sh[8], Q[8], R[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -283,7 +267,7 @@ __global__ void gn_apply2_kernel(GnApplyParams p) {
       R[e] = -rs * c1 + mu * rs * rs * c2;
     }
   }
-  for (int pix = p0 + pl; pix < p1; pix += p.pxt) {
+  for (int pix = w.p0 + w.pl; pix < w.p1; pix += p.pxt) {
     const long row = (long)b * p.HW + pix;
     const bf16x8 x = ld8(p.X + row * p.ldx + 8 * vec);
     bf16x8 o;
@@ -308,56 +292,12 @@ __global__ void gn_apply2_kernel(GnApplyParams p) {
   }
 }
 
-int launch_gn_apply2(bool bwd, GnApplyParams& p, int B, hipStream_t stream) {
-  const int nvec_total = p.C >> 3;
-  const int zsplit = (nvec_total + 511) / 512;
-  const int nvec = nvec_total < 512 ? nvec_total : 512;
-  int pxt = 256 / nvec;
-  if (pxt < 1) pxt = 1;
-  if (pxt > p.HW) pxt = p.HW;
-  p.pxt = pxt;
-  // enough (image, pixel-chunk) workgroups to keep >= 8 waves per CU busy, >= 4 pixels per thread
-  int nch = (4096 + B * zsplit - 1) / (B * zsplit);
-  int maxc = p.HW / (4 * pxt);
-  if (nch > maxc) nch = maxc;
-  if (nch < 1) nch = 1;
-  p.nchunks = nch;
-  p.ppc = (p.HW + nch - 1) / nch;
-  dim3 grid(nch, B, zsplit), block(nvec * pxt);
-  if (bwd) hipLaunchKernelGGL(gn_apply2_kernel<true>, grid, block, 0, stream, p);
-  else hipLaunchKernelGGL(gn_apply2_kernel<false>, grid, block, 0, stream, p);
+int launch_gn_apply2(bool bwd, WalkParams& p, int B, hipStream_t stream) {
+  dim3 grid, block;
+  walk_geometry(p, B, 256, 0, grid, block);
+  hipLaunchKernelGGL(bwd ? gn_apply2_kernel<true> : gn_apply2_kernel<false>, grid, block, 0, stream, p);
   DA_CHECK_LAUNCH();
   return DA_OK;
-}
-
-// dx = rstd * (dz*gamma - c1 - xhat*c2) (+ Radd)
-__global__ void gn_bwd_apply_kernel(const bf16* X, long ldx, const bf16* DY, long lddy, const bf16* Radd, long ldr,
-                                    bf16* DX, long lddx, const float* mean_rstd, const float* coef,
-                                    const float* gamma, const float* beta, int HW, int C, int G, int cpg,
-                                    long total_vec, int silu) {
-  const int nvec = C >> 3;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec; i += (long)gridDim.x * blockDim.x) {
-    long row = i / nvec;
-    int vec = (int)(i - row * nvec);
-    int b = (int)(row / HW);
-    bf16x8 x = ld8(X + row * ldx + 8 * vec);
-    bf16x8 dy = ld8(DY + row * lddy + 8 * vec);
-    bf16x8 ra = Radd ? ld8(Radd + row * ldr + 8 * vec) : zero8();
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int c = 8 * vec + e;
-      int g = c / cpg;
-      const float mu = mean_rstd[((long)b * G + g) * 2], rs = mean_rstd[((long)b * G + g) * 2 + 1];
-      const float c1 = coef[((long)b * G + g) * 2], c2 = coef[((long)b * G + g) * 2 + 1];
-      float xh = (bf2f(x[e]) - mu) * rs;
-      float dz = bf2f(dy[e]);
-      if (silu) dz *= dsilu_f(xh * gamma[c] + beta[c]);
-      float dx = rs * (dz * gamma[c] - c1 - xh * c2);
-      o[e] = f2bf(dx + bf2f(ra[e]));
-    }
-    st8(DX + row * lddx + 8 * vec, o);
-  }
 }
 
 // out1[c] += sum_rows partial[row][c][0] ; out2[c] += sum_rows partial[row][c][1]
@@ -366,9 +306,32 @@ __global__ void gn_bwd_apply_kernel(const bf16* X, long ldx, const bf16* DY, lon
 // row-lanes meet in LDS and thread (0, cx) adds them in lane order.  The earlier form sliced the rows over blockIdx.y and
 // let the slices meet in fp32 atomics (order-dependent last bits in every norm / bias gradient).
 constexpr int CSF_CH = 16, CSF_RL = 64;
+
+// The fixed-order meeting of the row-lanes: v (float, or float2 for two sums at once) of row-lane ry, channel lane cx
+// -> 64 row-lanes -> 8 -> 1, every level in index order.  Row-lane 0 returns the total, the other lanes zero.
+template <typename T>
+DEVINL T lane_fold(T (&sh)[CSF_RL][CSF_CH], int ry, int cx, T v) {
+  sh[ry][cx] = v;
+  __syncthreads();
+  T l = {};
+  if (ry < 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) l += sh[ry * 8 + j][cx];
+  }
+  __syncthreads();
+  if (ry < 8) sh[ry][cx] = l;
+  __syncthreads();
+  T t = {};
+  if (ry == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t += sh[j][cx];
+  }
+  return t;
+}
+
 __global__ __launch_bounds__(CSF_CH * CSF_RL) void chan_sum_finalize_kernel(const float* partial, int nrows, int C,
                                                                             float* out1, float* out2, int overwrite) {
-  __shared__ float sh[CSF_RL][CSF_CH][2];
+  __shared__ float2 sh[CSF_RL][CSF_CH];
   const int cx = threadIdx.x % CSF_CH, ry = threadIdx.x / CSF_CH;
   const int c = blockIdx.x * CSF_CH + cx;
   float a = 0.f, q = 0.f;
@@ -392,39 +355,19 @@ __global__ __launch_bounds__(CSF_CH * CSF_RL) void chan_sum_finalize_kernel(cons
     a = (a0 + a1) + (a2 + a3);
     q = (q0 + q1) + (q2 + q3);
   }
-  sh[ry][cx][0] = a;
-  sh[ry][cx][1] = q;
-  __syncthreads();
-  // 64 row-lanes -> 8 -> 1, every level in index order
-  float la = 0.f, lq = 0.f;
-  if (ry < 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      la += sh[ry * 8 + j][cx][0];
-      lq += sh[ry * 8 + j][cx][1];
-    }
-  }
-  __syncthreads();
-  if (ry < 8) {
-    sh[ry][cx][0] = la;
-    sh[ry][cx][1] = lq;
-  }
-  __syncthreads();
+  const float2 t = lane_fold(sh, ry, cx, make_float2(a, q));
   if (ry == 0 && c < C) {
-    float ta = 0.f, tq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      ta += sh[j][cx][0];
-      tq += sh[j][cx][1];
-    }
-    if (out1) out1[c] = overwrite ? ta : out1[c] + ta;
-    if (out2) out2[c] = overwrite ? tq : out2[c] + tq;
+    if (out1) out1[c] = overwrite ? t.x : out1[c] + t.x;
+    if (out2) out2[c] = overwrite ? t.y : out2[c] + t.y;
   }
 }
 
-static inline dim3 chan_sum_grid(int nrows, int C) {
-  (void)nrows;
-  return dim3((C + CSF_CH - 1) / CSF_CH);
+// out1 / out2 (either may be NULL) over nrows partial rows of [C][2]; adds, or writes under grad_overwrite
+int launch_chan_sum(const float* partial, int nrows, int C, float* out1, float* out2, hipStream_t stream) {
+  hipLaunchKernelGGL(chan_sum_finalize_kernel, dim3((C + CSF_CH - 1) / CSF_CH), dim3(CSF_CH * CSF_RL), 0, stream, partial,
+                     nrows, C, out1, out2, g_grad_overwrite);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
 }
 
 // out[b][c] = sum_chunks partial[b][chunk][c][0] (bf16, strided) ; db[c] += sum_b out[b][c] (fp32)
@@ -451,22 +394,8 @@ __global__ __launch_bounds__(CSF_CH * CSF_RL) void image_colsum_finalize_kernel(
       tot += a;
     }
   }
-  sh[ry][cx] = tot;
-  __syncthreads();
-  float lt = 0.f;
-  if (ry < 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lt += sh[ry * 8 + j][cx];
-  }
-  __syncthreads();
-  if (ry < 8) sh[ry][cx] = lt;
-  __syncthreads();
-  if (ry == 0 && c < C && db) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t += sh[j][cx];
-    db[c] = overwrite ? t : db[c] + t;
-  }
+  const float t = lane_fold(sh, ry, cx, tot);
+  if (ry == 0 && c < C && db) db[c] = overwrite ? t : db[c] + t;
 }
 
 // ---- LayerNorm: one wave per row, row kept in registers (C <= 1536)
@@ -1107,6 +1036,25 @@ __global__ __launch_bounds__(T) void gn_res_bwd_kernel(GnResParams p) {
   }
 }
 
+// The compiled NL (data vectors per thread) of the resident kernels, ascending; a call with nl vectors runs the smallest
+// instantiation >= nl.  gn_res_plan's limits, gn_res_nl_inst and the dispatch all read these lists.
+using GnResFwdNL = std::integer_sequence<int, 1, 2, 3, 4, 6, 8, 11, 16, 21>;   // 1024 threads
+using GnResBwdNL = std::integer_sequence<int, 1, 2, 3, 4, 6, 8, 11>;           // 1024 threads, two resident tensors
+using GnResBwd768NL = std::integer_sequence<int, 11, 14>;                      // 768 threads (168 VGPRs)
+
+template <int... V>
+constexpr int nl_last(std::integer_sequence<int, V...>) {
+  int last = 0;
+  ((last = V), ...);
+  return last;
+}
+template <int... V>
+constexpr int nl_inst(std::integer_sequence<int, V...> list, int nl) {
+  int inst = 0;
+  ((inst = (!inst && nl <= V) ? V : inst), ...);
+  return inst ? inst : nl_last(list);
+}
+
 // Slab geometry for (B, HW, C, G): CW = whole groups, whole 16-B vectors, NL data vectors per thread <= max_nl.
 // Prefers line-aligned segments, then the widest part that still gives every CU a workgroup.  false -> no fit (the
 // multi-pass kernels take the call).
@@ -1116,11 +1064,12 @@ bool gn_res_plan(int B, int HW, int C, int G, long ld_min, long ld_max, bool bwd
   while (unit & 7) unit += cpg;                 // lcm(cpg, 8)
   if (unit > C || (C % unit)) return false;
   if ((long)HW * ld_max * 2 >= (1L << 31)) return false;   // 32-bit byte offsets inside an image
-  // forward: 1024 threads, <= 21 vectors each.  backward (two resident tensors): 1024 threads x <= 8 vectors, or 768
-  // threads (168 VGPRs) x <= 14
+  // forward: 1024 threads, <= 21 vectors each.  backward (two resident tensors): 1024 threads x <= 11 vectors (<= 8 under
+  // gn_resident_form = 2), or 768 threads (168 VGPRs) x <= 14
   const int nT = (bwd && g_gn_resident_form != 1) ? 2 : 1;
   const int Ts[2] = {1024, 768};
-  const int maxnl[2] = {bwd ? (g_gn_resident_form == 2 ? 8 : 11) : 21, 14};
+  const int maxnl[2] = {bwd ? (g_gn_resident_form == 2 ? 8 : nl_last(GnResBwdNL{})) : nl_last(GnResFwdNL{}),
+                        nl_last(GnResBwd768NL{})};
   double best = 1e30;
   int best_cw = 0, best_t = 0;
   for (int ti = 0; ti < nT; ++ti) {
@@ -1160,75 +1109,78 @@ bool gn_res_plan(int B, int HW, int C, int G, long ld_min, long ld_max, bool bwd
   return true;
 }
 
-template <int NL, bool SILU>
-int launch_gn_res_fwd2(const GnResParams& p, int B, hipStream_t stream) {
+// one resident launch: NL, the SiLU flag and the direction pick the kernel; T threads per workgroup
+template <int NL, int T, bool BWD>
+int launch_gn_res(const GnResParams& p, int B, hipStream_t stream) {
   const size_t smem = gn_res_lds_floats(p.P, p.CW, p.nseg, p.cpg) * sizeof(float);
   if (smem > 160 * 1024) return DA_ERR_SHAPE;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (da_ensure_dyn_smem((const void*)gn_res_fwd_kernel<NL, SILU>, 160 * 1024, &attr_done) != DA_OK) return DA_ERR_LAUNCH;
-  hipLaunchKernelGGL((gn_res_fwd_kernel<NL, SILU>), dim3(B * p.parts), dim3(1024), smem, stream, p);
+  void (*kernel)(GnResParams);
+  if constexpr (BWD) kernel = p.silu ? gn_res_bwd_kernel<NL, true, T> : gn_res_bwd_kernel<NL, false, T>;
+  else kernel = p.silu ? gn_res_fwd_kernel<NL, true> : gn_res_fwd_kernel<NL, false>;
+  static unsigned long long attr_done[2] = {0, 0};  // per kernel (SiLU off / on): one bit per device
+  if (da_ensure_dyn_smem((const void*)kernel, 160 * 1024, &attr_done[p.silu != 0]) != DA_OK) return DA_ERR_LAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(B * p.parts), dim3(T), smem, stream, p);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
 
-template <int NL>
-int launch_gn_res_fwd(const GnResParams& p, int B, hipStream_t stream) {
-  return p.silu ? launch_gn_res_fwd2<NL, true>(p, B, stream) : launch_gn_res_fwd2<NL, false>(p, B, stream);
+template <int T, bool BWD, int... V>
+int dispatch_gn_res(std::integer_sequence<int, V...> list, int nl, const GnResParams& p, int B, hipStream_t stream) {
+  const int inst = nl_inst(list, nl);
+  int rc = DA_ERR_SHAPE;
+  ((inst == V ? (void)(rc = launch_gn_res<V, T, BWD>(p, B, stream)) : (void)0), ...);
+  return rc;
 }
 
-template <int NL, bool SILU, int T>
-int launch_gn_res_bwd2(const GnResParams& p, int B, hipStream_t stream) {
-  const size_t smem = gn_res_lds_floats(p.P, p.CW, p.nseg, p.cpg) * sizeof(float);
-  if (smem > 160 * 1024) return DA_ERR_SHAPE;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (da_ensure_dyn_smem((const void*)gn_res_bwd_kernel<NL, SILU, T>, 160 * 1024, &attr_done) != DA_OK) return DA_ERR_LAUNCH;
-  hipLaunchKernelGGL((gn_res_bwd_kernel<NL, SILU, T>), dim3(B * p.parts), dim3(T), smem, stream, p);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-
-template <int NL, int T>
-int launch_gn_res_bwd(const GnResParams& p, int B, hipStream_t stream) {
-  return p.silu ? launch_gn_res_bwd2<NL, true, T>(p, B, stream) : launch_gn_res_bwd2<NL, false, T>(p, B, stream);
-}
-
-// the NL instantiation that runs nl data vectors per thread: the smallest compiled one >= nl (da_groupnorm_plan_for reports it)
+// the NL instantiation that runs nl data vectors per thread (da_groupnorm_plan_for reports it)
 int gn_res_nl_inst(int nl, bool bwd, int threads) {
-  if (bwd && threads == 768) return nl <= 11 ? 11 : 14;
-  static const int fwd[] = {1, 2, 3, 4, 6, 8, 11, 16, 21}, bwd1024[] = {1, 2, 3, 4, 6, 8, 11};
-  const int* v = bwd ? bwd1024 : fwd;
-  const int n = bwd ? 7 : 9;
-  for (int i = 0; i < n - 1; ++i)
-    if (nl <= v[i]) return v[i];
-  return v[n - 1];
+  if (!bwd) return nl_inst(GnResFwdNL{}, nl);
+  return threads == 768 ? nl_inst(GnResBwd768NL{}, nl) : nl_inst(GnResBwdNL{}, nl);
 }
 
-int dispatch_gn_res_fwd(int nl, const GnResParams& p, int B, hipStream_t s) {
-  switch (gn_res_nl_inst(nl, false, 1024)) {
-    case 1: return launch_gn_res_fwd<1>(p, B, s);
-    case 2: return launch_gn_res_fwd<2>(p, B, s);
-    case 3: return launch_gn_res_fwd<3>(p, B, s);
-    case 4: return launch_gn_res_fwd<4>(p, B, s);
-    case 6: return launch_gn_res_fwd<6>(p, B, s);
-    case 8: return launch_gn_res_fwd<8>(p, B, s);
-    case 11: return launch_gn_res_fwd<11>(p, B, s);
-    case 16: return launch_gn_res_fwd<16>(p, B, s);
-    default: return launch_gn_res_fwd<21>(p, B, s);
-  }
+bool gn_args_ok(int B, int HW, int C, int G, long lds_ored) {
+  return B > 0 && HW > 0 && C > 0 && G > 0 && !(C % G) && !(C & 7) && !(lds_ored & 7);
 }
 
-int dispatch_gn_res_bwd(int nl, int threads, const GnResParams& p, int B, hipStream_t s) {
-  if (threads == 768) return gn_res_nl_inst(nl, true, 768) == 11 ? launch_gn_res_bwd<11, 768>(p, B, s)
-                                                                  : launch_gn_res_bwd<14, 768>(p, B, s);
-  switch (gn_res_nl_inst(nl, true, 1024)) {
-    case 1: return launch_gn_res_bwd<1, 1024>(p, B, s);
-    case 2: return launch_gn_res_bwd<2, 1024>(p, B, s);
-    case 3: return launch_gn_res_bwd<3, 1024>(p, B, s);
-    case 4: return launch_gn_res_bwd<4, 1024>(p, B, s);
-    case 6: return launch_gn_res_bwd<6, 1024>(p, B, s);
-    case 8: return launch_gn_res_bwd<8, 1024>(p, B, s);
-    default: return launch_gn_res_bwd<11, 1024>(p, B, s);
-  }
+// The resident plan of a call: ld_a / ld_b / ld_c are the row strides every plan rule sees, ld_radd (0 = no Radd) only
+// bounds the 32-bit offsets.  Fills the geometry and the shape fields of r; false -> the multi-pass kernels take the call.
+bool gn_res_prepare(int B, int HW, int C, int G, long ld_a, long ld_b, long ld_c, long ld_radd, bool bwd, GnResParams& r,
+                    int& nl, int& threads) {
+  if (!g_gn_resident) return false;
+  const long ld_min = std::min({ld_a, ld_b, ld_c}), ld_max = std::max({ld_a, ld_b, ld_c, ld_radd});
+  if (!gn_res_plan(B, HW, C, G, ld_min, ld_max, bwd, r, nl, threads)) return false;
+  r.HW = HW; r.C = C; r.G = G; r.cpg = C / G;
+  r.inv_n = 1.0f / ((float)(C / G) * (float)HW);
+  return true;
+}
+
+// C = 40 * LPR takes the ln_*5 kernels: lanes per row, 0 for the one-row-per-wave kernels
+int ln5_lpr(int C) { return C == 320 ? 8 : C == 640 ? 16 : C == 1280 ? 32 : 0; }
+
+template <int LPR>
+int launch_ln_fwd5(const bf16* X, long ldx, bf16* Y, long ldy, const float* gamma, const float* beta, float* mean_rstd, int M,
+                   float eps, hipStream_t stream) {
+  constexpr int rpw = 64 / LPR;
+  long b5 = ((long)M + 4 * rpw - 1) / (4 * rpw);
+  if (b5 > 2048) b5 = 2048;
+  hipLaunchKernelGGL(ln_fwd5_kernel<LPR>, dim3((int)b5), dim3(256), 0, stream, X, ldx, Y, ldy, gamma, beta, mean_rstd, M, eps);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+template <int LPR>
+int launch_ln_bwd5(const bf16* X, long ldx, const bf16* dY, long lddy, const bf16* Radd, long ldr, bf16* dX, long lddx,
+                   const float* gamma, const float* mean_rstd, float* dgamma, float* dbeta, float* scratch, int M,
+                   hipStream_t stream) {
+  constexpr int rpw = 64 / LPR;
+  // >= 8 row groups per wave amortise the dgamma/dbeta fold; <= 1024 partial rows in scratch (da_norm_scratch_floats)
+  long b5 = ((long)M + 32 * rpw - 1) / (32 * rpw);
+  if (b5 < 256) b5 = ((long)M + 4 * rpw - 1) / (4 * rpw) < 256 ? ((long)M + 4 * rpw - 1) / (4 * rpw) : 256;
+  if (b5 > 1024) b5 = 1024;
+  hipLaunchKernelGGL((Radd ? ln_bwd5_kernel<LPR, true> : ln_bwd5_kernel<LPR, false>), dim3((int)b5), dim3(256), 0, stream, X,
+                     ldx, dY, lddy, Radd, ldr, dX, lddx, gamma, mean_rstd, scratch, M);
+  DA_CHECK_LAUNCH();
+  return launch_chan_sum(scratch, (int)b5, 40 * LPR, dgamma, dbeta, stream);
 }
 
 }  // namespace
@@ -1241,10 +1193,10 @@ extern "C" long da_norm_scratch_floats(int B, int HW, int C) {
 }
 
 extern "C" int da_groupnorm_plan_for(int B, int HW, int C, int G, long ld_min, long ld_max, int bwd, int* out) {
-  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 7) || (ld_min & 7) || (ld_max & 7) || !out) return -1;
+  if (!gn_args_ok(B, HW, C, G, ld_min | ld_max) || !out) return -1;
   GnResParams r = {};
   int nl = 0, threads = 0;
-  if (g_gn_resident && gn_res_plan(B, HW, C, G, ld_min, ld_max, bwd != 0, r, nl, threads)) {
+  if (gn_res_prepare(B, HW, C, G, ld_min, ld_max, ld_max, 0, bwd != 0, r, nl, threads)) {
     const int o[7] = {threads, gn_res_nl_inst(nl, bwd != 0, threads), r.CW, r.parts, r.peers8, r.P, 0};
     for (int i = 0; i < 7; ++i) out[i] = o[i];
     return 1;
@@ -1255,34 +1207,26 @@ extern "C" int da_groupnorm_plan_for(int B, int HW, int C, int G, long ld_min, l
 }
 
 extern "C" int da_groupnorm_fwd(const void* X, long ldx, void* Y, long ldy, const float* gamma, const float* beta,
-                                float* mean_rstd, float* scale_shift, float* scratch, int B, int HW, int C, int G,
-                                float eps, int silu, hipStream_t stream) {
+                                float* mean_rstd, float* /* scale_shift: unused, never written */, float* scratch, int B,
+                                int HW, int C, int G, float eps, int silu, hipStream_t stream) {
   DA_CLEAR_ERR();
-  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 7) || (ldx & 7) || (ldy & 7)) return DA_ERR_SHAPE;
-  if (g_gn_resident) {
-    GnResParams r = {};
-    int nl = 0, threads = 0;
-    if (gn_res_plan(B, HW, C, G, ldx < ldy ? ldx : ldy, ldx > ldy ? ldx : ldy, false, r, nl, threads)) {
-      r.X = (const bf16*)X; r.ldx = ldx; r.OUT = (bf16*)Y; r.ldo = ldy; r.gamma = gamma; r.beta = beta;
-      r.mean_rstd = mean_rstd; r.HW = HW; r.C = C; r.G = G; r.cpg = C / G; r.silu = silu; r.eps = eps;
-      r.inv_n = 1.0f / ((float)(C / G) * (float)HW);
-      return dispatch_gn_res_fwd(nl, r, B, stream);
-    }
+  if (!gn_args_ok(B, HW, C, G, ldx | ldy)) return DA_ERR_SHAPE;
+  GnResParams r = {};
+  int nl = 0, threads = 0;
+  if (gn_res_prepare(B, HW, C, G, ldx, ldy, ldy, 0, false, r, nl, threads)) {
+    r.X = (const bf16*)X; r.ldx = ldx; r.OUT = (bf16*)Y; r.ldo = ldy; r.gamma = gamma; r.beta = beta;
+    r.mean_rstd = mean_rstd; r.silu = silu; r.eps = eps;
+    return dispatch_gn_res<1024, false>(GnResFwdNL{}, nl, r, B, stream);
   }
-  ChanReduceParams p = {};
-  p.X = (const bf16*)X; p.ldx = ldx; p.partial = scratch;
-  p.HW = HW; p.C = C; p.G = G; p.cpg = C / G; p.nchunks = pick_chunks(B, HW);
-  int rc = launch_chan_reduce(0, p, B, stream);
+  WalkParams p = {};
+  p.X = (const bf16*)X; p.ldx = ldx; p.OUT = (bf16*)Y; p.ldo = ldy; p.partial = scratch;
+  p.mean_rstd = mean_rstd; p.gamma = gamma; p.beta = beta;
+  p.HW = HW; p.C = C; p.G = G; p.cpg = C / G; p.silu = silu;
+  int rc = launch_chan_reduce(0, p, B, pick_chunks(B, HW), stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_fwd_finalize_kernel, dim3(B, (G + GN_GPB - 1) / GN_GPB), dim3(256),
-                     (size_t)(2 * GN_GPB * (C / G) + 2 * GN_GPB) * sizeof(float), stream,
-                     scratch, gamma, beta, mean_rstd, scale_shift, C, G, C / G, p.nchunks, HW, eps);
-  DA_CHECK_LAUNCH();
-  GnApplyParams ap = {};
-  ap.X = (const bf16*)X; ap.ldx = ldx; ap.OUT = (bf16*)Y; ap.ldo = ldy;
-  ap.mean_rstd = mean_rstd; ap.gamma = gamma; ap.beta = beta;
-  ap.HW = HW; ap.C = C; ap.G = G; ap.cpg = C / G; ap.silu = silu;
-  return launch_gn_apply2(false, ap, B, stream);
+  rc = launch_gn_finalize(false, scratch, nullptr, mean_rstd, B, C, G, p.nchunks, HW, eps, stream);
+  if (rc) return rc;
+  return launch_gn_apply2(false, p, B, stream);
 }
 
 extern "C" int da_groupnorm_bwd(const void* X, long ldx, const void* dY, long lddy, const void* Radd, long ldr,
@@ -1290,79 +1234,57 @@ extern "C" int da_groupnorm_bwd(const void* X, long ldx, const void* dY, long ld
                                 float* dgamma, float* dbeta, float* coef, float* scratch, int B, int HW, int C, int G,
                                 int silu, hipStream_t stream) {
   DA_CLEAR_ERR();
-  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 7) || (ldx & 7) || (lddy & 7) || (lddx & 7))
-    return DA_ERR_SHAPE;
-  if (Radd && (ldr & 7)) return DA_ERR_SHAPE;
-  if (g_gn_resident) {
-    GnResParams r = {};
-    int nl = 0, threads = 0;
-    long ldm = ldx < lddy ? ldx : lddy, ldM = ldx > lddy ? ldx : lddy;
-    if (lddx < ldm) ldm = lddx;
-    if (lddx > ldM) ldM = lddx;
-    if (Radd && ldr > ldM) ldM = ldr;
-    if (gn_res_plan(B, HW, C, G, ldm, ldM, true, r, nl, threads)) {
-      r.X = (const bf16*)X; r.ldx = ldx; r.DY = (const bf16*)dY; r.lddy = lddy; r.Radd = (const bf16*)Radd; r.ldr = ldr;
-      r.OUT = (bf16*)dX; r.ldo = lddx; r.gamma = gamma; r.beta = beta; r.mean_rstd = const_cast<float*>(mean_rstd);
-      r.partial = scratch; r.HW = HW; r.C = C; r.G = G; r.cpg = C / G; r.silu = silu;
-      r.inv_n = 1.0f / ((float)(C / G) * (float)HW);
-      int rc = dispatch_gn_res_bwd(nl, threads, r, B, stream);
-      if (rc) return rc;
-      // dbeta[c] (+)= sum_b s1, dgamma[c] (+)= sum_b s2: one partial row per image
-      hipLaunchKernelGGL(chan_sum_finalize_kernel, chan_sum_grid(B, C), dim3(CSF_CH * CSF_RL), 0, stream, scratch, B, C, dbeta,
-                         dgamma, g_grad_overwrite);
-      DA_CHECK_LAUNCH();
-      return DA_OK;
-    }
+  if (!gn_args_ok(B, HW, C, G, ldx | lddy | lddx | (Radd ? ldr : 0))) return DA_ERR_SHAPE;
+  GnResParams r = {};
+  int nl = 0, threads = 0;
+  if (gn_res_prepare(B, HW, C, G, ldx, lddy, lddx, Radd ? ldr : 0, true, r, nl, threads)) {
+    r.X = (const bf16*)X; r.ldx = ldx; r.DY = (const bf16*)dY; r.lddy = lddy; r.Radd = (const bf16*)Radd; r.ldr = ldr;
+    r.OUT = (bf16*)dX; r.ldo = lddx; r.gamma = gamma; r.beta = beta; r.mean_rstd = const_cast<float*>(mean_rstd);
+    r.partial = scratch; r.silu = silu;
+    int rc = threads == 768 ? dispatch_gn_res<768, true>(GnResBwd768NL{}, nl, r, B, stream)
+                            : dispatch_gn_res<1024, true>(GnResBwdNL{}, nl, r, B, stream);
+    if (rc) return rc;
+    // dbeta[c] (+)= sum_b s1, dgamma[c] (+)= sum_b s2: one partial row per image
+    return launch_chan_sum(scratch, B, C, dbeta, dgamma, stream);
   }
-  ChanReduceParams p = {};
-  p.X = (const bf16*)X; p.ldx = ldx; p.DY = (const bf16*)dY; p.lddy = lddy;
-  p.mean_rstd = mean_rstd; p.gamma = gamma; p.beta = beta; p.partial = scratch;
-  p.HW = HW; p.C = C; p.G = G; p.cpg = C / G; p.nchunks = pick_chunks(B, HW); p.silu = silu;
-  int rc = launch_chan_reduce(1, p, B, stream);
+  WalkParams p = {};
+  p.X = (const bf16*)X; p.ldx = ldx; p.DY = (const bf16*)dY; p.lddy = lddy; p.Radd = (const bf16*)Radd; p.ldr = ldr;
+  p.OUT = (bf16*)dX; p.ldo = lddx; p.partial = scratch;
+  p.mean_rstd = mean_rstd; p.coef = coef; p.gamma = gamma; p.beta = beta;
+  p.HW = HW; p.C = C; p.G = G; p.cpg = C / G; p.silu = silu;
+  int rc = launch_chan_reduce(1, p, B, pick_chunks(B, HW), stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B, (G + GN_GPB - 1) / GN_GPB), dim3(256),
-                     (size_t)(2 * GN_GPB * (C / G)) * sizeof(float), stream, scratch,
-                     gamma, coef, C, G, C / G, p.nchunks, HW);
-  DA_CHECK_LAUNCH();
+  rc = launch_gn_finalize(true, scratch, gamma, coef, B, C, G, p.nchunks, HW, 0.f, stream);
+  if (rc) return rc;
   // dgamma[c] += sum_b s2, dbeta[c] += sum_b s1
-  hipLaunchKernelGGL(chan_sum_finalize_kernel, chan_sum_grid(B * p.nchunks, C), dim3(CSF_CH * CSF_RL), 0, stream, scratch,
-                     B * p.nchunks, C, dbeta, dgamma, g_grad_overwrite);
-  DA_CHECK_LAUNCH();
-  GnApplyParams ap = {};
-  ap.X = (const bf16*)X; ap.ldx = ldx; ap.DY = (const bf16*)dY; ap.lddy = lddy; ap.Radd = (const bf16*)Radd; ap.ldr = ldr;
-  ap.OUT = (bf16*)dX; ap.ldo = lddx;
-  ap.mean_rstd = mean_rstd; ap.coef = coef; ap.gamma = gamma; ap.beta = beta;
-  ap.HW = HW; ap.C = C; ap.G = G; ap.cpg = C / G; ap.silu = silu;
-  return launch_gn_apply2(true, ap, B, stream);
+  rc = launch_chan_sum(scratch, B * p.nchunks, C, dbeta, dgamma, stream);
+  if (rc) return rc;
+  return launch_gn_apply2(true, p, B, stream);
 }
 
 extern "C" int da_colsum_accum(const void* X, long ldx, float* out, float* scratch, int M, int C,
                                hipStream_t stream) {
   DA_CLEAR_ERR();
   if (M <= 0 || C <= 0 || (C & 7) || (ldx & 7)) return DA_ERR_SHAPE;
-  ChanReduceParams p = {};
+  WalkParams p = {};
   p.X = (const bf16*)X; p.ldx = ldx; p.partial = scratch;
   p.HW = M; p.C = C; p.G = 1; p.cpg = C;
   int n = M / 64;
   if (n > 256) n = 256;
   if (n < 1) n = 1;
-  p.nchunks = n;
-  int rc = launch_chan_reduce(2, p, 1, stream);
+  int rc = launch_chan_reduce(2, p, 1, n, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(chan_sum_finalize_kernel, chan_sum_grid(n, C), dim3(CSF_CH * CSF_RL), 0, stream, scratch, n, C, out,
-                     (float*)nullptr, g_grad_overwrite);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return launch_chan_sum(scratch, n, C, out, nullptr, stream);
 }
 
 extern "C" int da_image_colsum(const void* X, long ldx, void* out, long ldo, float* db, float* scratch, int B, int HW,
                                int C, hipStream_t stream) {
   DA_CLEAR_ERR();
   if (B <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldx & 7)) return DA_ERR_SHAPE;
-  ChanReduceParams p = {};
+  WalkParams p = {};
   p.X = (const bf16*)X; p.ldx = ldx; p.partial = scratch;
-  p.HW = HW; p.C = C; p.G = 1; p.cpg = C; p.nchunks = pick_chunks(B, HW);
-  int rc = launch_chan_reduce(2, p, B, stream);
+  p.HW = HW; p.C = C; p.G = 1; p.cpg = C;
+  int rc = launch_chan_reduce(2, p, B, pick_chunks(B, HW), stream);
   if (rc) return rc;
   hipLaunchKernelGGL(image_colsum_finalize_kernel, dim3((C + CSF_CH - 1) / CSF_CH), dim3(CSF_CH * CSF_RL), 0, stream,
                      scratch, (bf16*)out, ldo, db, B, p.nchunks, C, g_grad_overwrite);
@@ -1374,16 +1296,9 @@ extern "C" int da_layernorm_fwd(const void* X, long ldx, void* Y, long ldy, cons
                                 float* mean_rstd, int M, int C, float eps, hipStream_t stream) {
   DA_CLEAR_ERR();
   if (M <= 0 || C <= 0 || (C & 7) || C > 8 * 64 * LN_MAXV || (ldx & 7) || (ldy & 7)) return DA_ERR_SHAPE;
-  if (C == 320 || C == 640 || C == 1280) {
-    const int rpw = 64 / (C / 40);
-    long b5 = ((long)M + 4 * rpw - 1) / (4 * rpw);
-    if (b5 > 2048) b5 = 2048;
-#define LN_FWD5(L) hipLaunchKernelGGL(ln_fwd5_kernel<L>, dim3((int)b5), dim3(256), 0, stream, (const bf16*)X, ldx, \
-                                      (bf16*)Y, ldy, gamma, beta, mean_rstd, M, eps)
-    if (C == 320) LN_FWD5(8); else if (C == 640) LN_FWD5(16); else LN_FWD5(32);
-#undef LN_FWD5
-    DA_CHECK_LAUNCH();
-    return DA_OK;
+  if (const int lpr = ln5_lpr(C)) {
+    const auto launch = lpr == 8 ? launch_ln_fwd5<8> : lpr == 16 ? launch_ln_fwd5<16> : launch_ln_fwd5<32>;
+    return launch((const bf16*)X, ldx, (bf16*)Y, ldy, gamma, beta, mean_rstd, M, eps, stream);
   }
   int blocks = (M + 3) / 4;
   if (blocks > 4096) blocks = 4096;
@@ -1400,28 +1315,10 @@ extern "C" int da_layernorm_bwd(const void* X, long ldx, const void* dY, long ld
   if (M <= 0 || C <= 0 || (C & 7) || C > 8 * 64 * LN_MAXV || (ldx & 7) || (lddy & 7) || (lddx & 7))
     return DA_ERR_SHAPE;
   if (Radd && (ldr & 7)) return DA_ERR_SHAPE;
-  if (C == 320 || C == 640 || C == 1280) {
-    const int rpw = 64 / (C / 40);
-    // >= 8 row groups per wave amortise the dgamma/dbeta fold; <= 1024 partial rows in scratch (da_norm_scratch_floats)
-    long b5 = ((long)M + 32 * rpw - 1) / (32 * rpw);
-    if (b5 < 256) b5 = ((long)M + 4 * rpw - 1) / (4 * rpw) < 256 ? ((long)M + 4 * rpw - 1) / (4 * rpw) : 256;
-    if (b5 > 1024) b5 = 1024;
-#define LN_BWD5(L)                                                                                                   \
-  do {                                                                                                               \
-    if (Radd)                                                                                                        \
-      hipLaunchKernelGGL((ln_bwd5_kernel<L, true>), dim3((int)b5), dim3(256), 0, stream, (const bf16*)X, ldx,         \
-                         (const bf16*)dY, lddy, (const bf16*)Radd, ldr, (bf16*)dX, lddx, gamma, mean_rstd, scratch, M); \
-    else                                                                                                             \
-      hipLaunchKernelGGL((ln_bwd5_kernel<L, false>), dim3((int)b5), dim3(256), 0, stream, (const bf16*)X, ldx,        \
-                         (const bf16*)dY, lddy, (const bf16*)Radd, ldr, (bf16*)dX, lddx, gamma, mean_rstd, scratch, M); \
-  } while (0)
-    if (C == 320) LN_BWD5(8); else if (C == 640) LN_BWD5(16); else LN_BWD5(32);
-#undef LN_BWD5
-    DA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(chan_sum_finalize_kernel, chan_sum_grid((int)b5, C), dim3(CSF_CH * CSF_RL), 0, stream, scratch, (int)b5, C,
-                       dgamma, dbeta, g_grad_overwrite);
-    DA_CHECK_LAUNCH();
-    return DA_OK;
+  if (const int lpr = ln5_lpr(C)) {
+    const auto launch = lpr == 8 ? launch_ln_bwd5<8> : lpr == 16 ? launch_ln_bwd5<16> : launch_ln_bwd5<32>;
+    return launch((const bf16*)X, ldx, (const bf16*)dY, lddy, (const bf16*)Radd, ldr, (bf16*)dX, lddx, gamma, mean_rstd,
+                  dgamma, dbeta, scratch, M, stream);
   }
   int blocks = (M + 3) / 4;
   if (blocks > 1024) blocks = 1024;  // 4 waves each: >= 16 waves per CU in flight for this HBM-bound pass
@@ -1429,8 +1326,5 @@ extern "C" int da_layernorm_bwd(const void* X, long ldx, const void* dY, long ld
                      (const bf16*)X, ldx, (const bf16*)dY, lddy, (const bf16*)Radd, ldr, (bf16*)dX, lddx, gamma,
                      mean_rstd, scratch, M, C);
   DA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(chan_sum_finalize_kernel, chan_sum_grid(blocks, C), dim3(CSF_CH * CSF_RL), 0, stream, scratch, blocks, C,
-                     dgamma, dbeta, g_grad_overwrite);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return launch_chan_sum(scratch, blocks, C, dgamma, dbeta, stream);
 }

@@ -176,7 +176,8 @@ long da_norm_scratch_floats(int B, int HW, int C);
 
 /* GroupNorm (+ optional fused SiLU) over [B][HW][C], G groups.  Replaces torch.nn.GroupNorm / Composer
  * LPGroupNorm (train.py:91-99) + F.silu in ResnetBlock2D / Transformer2DModel / conv_norm_out.
- * mean_rstd[B][G][2] is saved for backward; scale_shift[B][C][2] is scratch (untouched when the single-pass form runs).
+ * mean_rstd[B][G][2] is saved for backward; scale_shift is unused and never written, by either form (the argument
+ * stays for the ABI; NULL is fine).
  * Single pass (see "gn_resident"): a 1024-thread workgroup owns HW pixels x CW channels (whole groups) of one image in
  * registers, so the tensor crosses HBM once in and once out; otherwise statistics, finalize and apply are three launches. */
 int da_groupnorm_fwd(const void* X, long ldx, void* Y, long ldy, const float* gamma, const float* beta,

@@ -4,7 +4,7 @@ strides, tails and inputs where norm kernels go wrong.
 GroupNorm forms (da_groupnorm_fwd / _bwd), forced with da_set_option:
 
     form      | gn_resident | gn_resident_form | kernels
-    multipass | 0           | -                | chan_reduce -> gn_fwd/bwd_finalize -> gn_apply2, pick_chunks(B, HW) pixel chunks
+    multipass | 0           | -                | chan_reduce -> gn_finalize<BWD> -> gn_apply2, pick_chunks(B, HW) pixel chunks
     res0/1/2  | 1           | 0 / 1 / 2        | gn_res_fwd<NL> / gn_res_bwd<NL, threads> where gn_res_plan takes the shape
 
 (the resident forms also set gn_resident_min_slab = 0).  GN_CASES pins, for every shape, the instantiation each forced form
@@ -332,6 +332,7 @@ def gn_fwd(ops, x, gamma, beta, B, HW, C, G, eps, silu, ld, seed):
     torch.cuda.synchronize()
     check_sentinels(ybuf, ybefore, B * HW, C, 'y')
     check_f32_sentinels(mbuf, mbefore, B * G * 2, 'mean_rstd')
+    assert torch.isnan(ss).all(), 'scale_shift: written (the buffer is unused by every form)'
     return y, mr
 
 

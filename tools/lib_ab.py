@@ -7,6 +7,8 @@ per cent, so numbers from different gpurun boxes are not comparable).
   python tools/lib_ab.py <old.so> gn                   GroupNorm(+SiLU) forward / backward at the U-Net's shapes
   python tools/lib_ab.py <old.so> pw                   the strided-map, noising and loss kernels of pointwise.hip, bit for bit
   python tools/lib_ab.py <old.so> smp                  the ten entries of sampler.hip (eight steps, init, guidance rescale), bit for bit
+  python tools/lib_ab.py <old.so> norms [bits|time]    every entry of norms.hip (GroupNorm under each forced form, LayerNorm, the
+                                                       column sums): bit for bit at the edge shapes, then timed at the U-Net's
 With candidates, each is timed against <old.so>; without, the shipped library is the candidate.
 
 <old.so> is any earlier build, e.g.  git show <rev>:diffusion_amd/csrc/attention.hip > /tmp/a.hip ; hipcc ... -o tools/_ab/old.so
@@ -436,8 +438,209 @@ def run(old, new, what):
         print(f'smp every comparison equal bits {ok_all}', flush=True)
         if not ok_all:
             raise SystemExit(1)
+    elif what == 'norms':
+        norms(old, new, dev, st, sys.argv[3] if len(sys.argv) > 3 and sys.argv[3] in ('bits', 'time') else 'all')
     else:
         raise SystemExit(__doc__)
+
+
+def norms(old, new, dev, st, part):
+    """every entry of norms.hip: all output buffers bit for bit at the edge shapes (part 'bits'), then time at the workload's
+    shapes (part 'time'); 'all' runs both.  Outputs start from a sentinel, so a stray or a missing store shows too."""
+    import itertools
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    from test_norm_edges_gpu import FORMS, GN_CASES, LN5_RPW, row_stride
+    BF = torch.bfloat16
+    bits = lambda t: t.view(torch.int16 if t.dtype == BF else torch.int32)   # noqa: E731  (NaN-proof)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    gen = torch.Generator(device=dev).manual_seed(9)
+    libs = (old, new)
+
+    def rnd(*shape, dtype=torch.float32):
+        return torch.randn(*shape, device=dev, generator=gen).to(dtype)
+
+    def sent(*shape, dtype=torch.float32):
+        return torch.full(shape, 7.0, device=dev, dtype=dtype)
+
+    def opt(key, value, only=libs):
+        for lib in only:
+            lib.da_set_option.argtypes = [_ct.c_char_p, _ct.c_int]
+            assert lib.da_set_option(key.encode(), int(value)) == 0, key
+
+    def view(t, ld):
+        """t [rows, C] as a column view at 8 of a [rows, ld] buffer (the other columns: sentinel)"""
+        buf = sent(t.shape[0], ld, dtype=BF)
+        buf[:, 8:8 + t.shape[1]] = t
+        return buf[:, 8:8 + t.shape[1]]
+
+    def same(a, b, skip=()):
+        return [k for k in a if k not in skip and not torch.equal(bits(a[k]), bits(b[k]))]
+
+    # ---- the calls: o = this build's own output buffers (whole strided buffers, so pad columns are compared too)
+    def gn_bufs(B, HW, C, G, ld, prior):
+        n = int(new.da_norm_scratch_floats(B, HW, C))
+        return dict(y=sent(B * HW, ld, dtype=BF), mean_rstd=sent(B * G * 2), scale_shift=sent(B * C * 2), scratch_f=sent(n),
+                    dx=sent(B * HW, ld, dtype=BF), coef=sent(B * G * 2), scratch_b=sent(n),
+                    dgamma=prior[0].clone() if prior else sent(C), dbeta=prior[1].clone() if prior else sent(C))
+
+    def gn_fwd(lib, o, x, gamma, beta, B, HW, C, G, ld, eps, silu):
+        return lib.da_groupnorm_fwd(ptr(x), ld, o['y'].data_ptr() + 16, ld, ptr(gamma), ptr(beta), ptr(o['mean_rstd']),
+                                    ptr(o['scale_shift']), ptr(o['scratch_f']), B, HW, C, G, eps, silu, st)
+
+    def gn_bwd(lib, o, x, dy, r, gamma, beta, B, HW, C, G, ld, silu):
+        return lib.da_groupnorm_bwd(ptr(x), ld, ptr(dy), ld, ptr(r), ld if r is not None else 0, o['dx'].data_ptr() + 16, ld, ptr(gamma),
+                                    ptr(beta), ptr(o['mean_rstd']), ptr(o['dgamma']), ptr(o['dbeta']), ptr(o['coef']),
+                                    ptr(o['scratch_b']), B, HW, C, G, silu, st)
+
+    def ln_bufs(M, C, prior):
+        return dict(y=sent(M, C, dtype=BF), mean_rstd=sent(2 * M), dx=sent(M, C, dtype=BF), scratch=sent(1024 * C * 2),
+                    dgamma=prior[0].clone() if prior else sent(C), dbeta=prior[1].clone() if prior else sent(C))
+
+    def ln_fwd(lib, o, x, gamma, beta, M, C):
+        return lib.da_layernorm_fwd(ptr(x), C, ptr(o['y']), C, ptr(gamma), ptr(beta), ptr(o['mean_rstd']), M, C, 1e-5, st)
+
+    def ln_bwd(lib, o, x, dy, r, gamma, M, C):
+        return lib.da_layernorm_bwd(ptr(x), C, ptr(dy), C, ptr(r), C if r is not None else 0, ptr(o['dx']), C, ptr(gamma),
+                                    ptr(o['mean_rstd']), ptr(o['dgamma']), ptr(o['dbeta']), ptr(o['scratch']), M, C, st)
+
+    def colsum(lib, o, x, M, C):
+        return lib.da_colsum_accum(ptr(x), C, ptr(o['out']), ptr(o['scratch']), M, C, st)
+
+    def image_colsum(lib, o, x, B, HW, C):
+        return lib.da_image_colsum(ptr(x), C, ptr(o['out']), C, ptr(o['db']), ptr(o['scratch']), B, HW, C, st)
+
+    ok_all = True
+
+    def report(label, n_cases, names, bad):
+        nonlocal ok_all
+        ok_all &= not bad
+        print(f'norms {label}: {n_cases} cases: {names}  equal bits {not bad}' + (f'  FIRST DIFFERENCES {bad[:4]}' if bad else ''),
+              flush=True)
+
+    if part in ('all', 'bits'):
+        # GroupNorm: the cases and strides of the edge tests under each forced form; gradients added onto a prior and written
+        for form, (case, _, _) in itertools.product(FORMS, GN_CASES):
+            B, HW, C, G, aligned, eps, silu, radd = case
+            ld = row_stride(C, aligned)
+            opt('gn_resident', FORMS[form][0]); opt('gn_resident_form', FORMS[form][1]); opt('gn_resident_min_slab', 0)
+            x, dy = view(rnd(B * HW, C, dtype=BF), ld), view(rnd(B * HW, C, dtype=BF), ld)
+            r = view(rnd(B * HW, C, dtype=BF), ld) if radd else None
+            gamma, beta, prior = 1 + 0.25 * rnd(C), 0.25 * rnd(C), (rnd(C), rnd(C))
+            bad = []
+            for overwrite in (0, 1):
+                opt('grad_overwrite', overwrite)
+                oa, ob = (gn_bufs(B, HW, C, G, ld, None if overwrite else prior) for _ in libs)
+                rcs = [gn_fwd(lib, o, x, gamma, beta, B, HW, C, G, ld, eps, silu) for lib, o in zip(libs, (oa, ob))]
+                rcs += [gn_bwd(lib, o, x, dy, r, gamma, beta, B, HW, C, G, ld, silu) for lib, o in zip(libs, (oa, ob))]
+                torch.cuda.synchronize()
+                # scale_shift is exempt from the comparison: the new build must leave the sentinel
+                diff = same(oa, ob, skip=('scale_shift',)) + ([] if torch.equal(ob['scale_shift'], sent(B * C * 2)) else ['scale_shift written'])
+                if any(rcs) or diff:
+                    bad.append((overwrite, rcs, diff))
+            opt('grad_overwrite', 0)
+            report(f'groupnorm {form:9s} {case}', 2, 'y mean_rstd dx coef dgamma dbeta scratch (grad_overwrite 0 / 1), scale_shift left alone', bad)
+        opt('gn_resident', 192); opt('gn_resident_form', 0); opt('gn_resident_min_slab', 64 * 1024)
+        # LayerNorm: the *5 kernels around the rows of a wave and past the capped grids, the generic ones at lane tails
+        ln_shapes = [(M, C) for C, rpw in LN5_RPW.items() for M in sorted({1, rpw - 1, rpw + 1, 4 * rpw + 1, 65539} - {0})]
+        ln_shapes += [(M, C) for C in (8, 64, 1024, 1536) for M in (1, 5, 4097)]
+        for M, C in ln_shapes:
+            x, dy, radd_t, gamma, beta, prior = rnd(M, C, dtype=BF), rnd(M, C, dtype=BF), rnd(M, C, dtype=BF), 1 + 0.25 * rnd(C), rnd(C), (rnd(C), rnd(C))
+            bad = []
+            for r, overwrite in itertools.product((None, radd_t), (0, 1)):
+                opt('grad_overwrite', overwrite)
+                oa, ob = (ln_bufs(M, C, None if overwrite else prior) for _ in libs)
+                rcs = [ln_fwd(lib, o, x, gamma, beta, M, C) for lib, o in zip(libs, (oa, ob))]
+                rcs += [ln_bwd(lib, o, x, dy, r, gamma, M, C) for lib, o in zip(libs, (oa, ob))]
+                torch.cuda.synchronize()
+                if any(rcs) or same(oa, ob):
+                    bad.append((r is not None, overwrite, rcs, same(oa, ob)))
+            opt('grad_overwrite', 0)
+            report(f'layernorm M={M} C={C}', 4, 'y mean_rstd dx dgamma dbeta scratch (Radd / none, grad_overwrite 0 / 1)', bad)
+        # column sums: every loop, tail, z-slab and lane fold
+        for M, C in ((1, 8), (63, 24), (12416, 16), (16421, 24), (16, 10240)):
+            x, prior, bad = rnd(M, C, dtype=BF), rnd(C), []
+            for overwrite in (0, 1):
+                opt('grad_overwrite', overwrite)
+                oa, ob = (dict(out=sent(C) if overwrite else prior.clone(), scratch=sent(256 * C * 2)) for _ in libs)
+                rcs = [colsum(lib, o, x, M, C) for lib, o in zip(libs, (oa, ob))]
+                torch.cuda.synchronize()
+                if any(rcs) or same(oa, ob):
+                    bad.append((overwrite, rcs, same(oa, ob)))
+            opt('grad_overwrite', 0)
+            report(f'colsum_accum M={M} C={C}', 2, 'out scratch (grad_overwrite 0 / 1)', bad)
+        for B, HW, C in ((1, 1, 8), (65, 512, 16), (130, 16, 4104)):
+            x, prior, bad = rnd(B * HW, C, dtype=BF), rnd(C), []
+            for with_db, overwrite in itertools.product((1, 0), (0, 1)):
+                opt('grad_overwrite', overwrite)
+                oa, ob = (dict(out=sent(B, C, dtype=BF), db=(sent(C) if overwrite else prior.clone()) if with_db else None,
+                               scratch=sent(int(new.da_norm_scratch_floats(B, HW, C)))) for _ in libs)
+                rcs = [image_colsum(lib, o, x, B, HW, C) for lib, o in zip(libs, (oa, ob))]
+                torch.cuda.synchronize()
+                diff = same({k: v for k, v in oa.items() if v is not None}, ob)
+                if any(rcs) or diff:
+                    bad.append((with_db, overwrite, rcs, diff))
+            opt('grad_overwrite', 0)
+            report(f'image_colsum B={B} HW={HW} C={C}', 4, 'out db scratch (db / NULL, grad_overwrite 0 / 1)', bad)
+        print(f'norms every comparison equal bits {ok_all}', flush=True)
+        if not ok_all:
+            raise SystemExit(1)
+    if part in ('all', 'time'):
+        # the workload: launches per window calibrated as in `pw`, 7 windows, 4 passes; an entry's rows are its samples for
+        # the closing "norms spread" line (with the same build on both sides: its noise)
+        spread = {}
+
+        def row(op, label, fa, fb):
+            fa(); fb(); torch.cuda.synchronize()
+            reps = max(5, min(20000, int(30e3 / max(timeit(fa, 20), 1e-3))))
+            ta, tb = ab(fa, fb, reps=reps, rounds=7)
+            pct = 100 * (ta / tb - 1)
+            spread.setdefault(op, []).append(pct)
+            print(f'norms {op:20s} {label:30s}: {ta:8.2f} -> {tb:8.2f} us ({pct:+5.1f} %, {reps} launches / window)', flush=True)
+
+        def ok(rc):
+            assert rc == 0, rc
+
+        for rep in (1, 2, 3, 4):
+            B, G = 256, 32
+            for HW, C in ((1024, 320), (1024, 960), (256, 640), (256, 1920), (64, 1280), (64, 2560), (16, 1280)):
+                x, dy, r = rnd(B * HW, C, dtype=BF), rnd(B * HW, C, dtype=BF), rnd(B * HW, C, dtype=BF)
+                gamma, beta = 1 + 0.25 * rnd(C), 0.25 * rnd(C)
+                oa, ob = (gn_bufs(B, HW, C, G, C, None) for _ in libs)
+                for tag, res in (('', 192), (' mp', 0)):      # the default options, then the multi-pass kernels
+                    opt('gn_resident', res)
+                    label = f'B={B} HW={HW} C={C} pass {rep}'
+
+                    def fwd(lib, o):
+                        ok(lib.da_groupnorm_fwd(ptr(x), C, ptr(o['y']), C, ptr(gamma), ptr(beta), ptr(o['mean_rstd']), ptr(o['scale_shift']),
+                                                ptr(o['scratch_f']), B, HW, C, G, 1e-5, 1, st))
+
+                    def bwd(lib, o, radd):
+                        ok(lib.da_groupnorm_bwd(ptr(x), C, ptr(dy), C, ptr(radd), C if radd is not None else 0, ptr(o['dx']), C, ptr(gamma),
+                                                ptr(beta), ptr(o['mean_rstd']), ptr(o['dgamma']), ptr(o['dbeta']), ptr(o['coef']),
+                                                ptr(o['scratch_b']), B, HW, C, G, 1, st))
+                    row('gn_fwd' + tag, label, lambda: fwd(old, oa), lambda: fwd(new, ob))
+                    row('gn_bwd' + tag, label, lambda: bwd(old, oa, None), lambda: bwd(new, ob, None))
+                    row('gn_bwd_radd' + tag, label, lambda: bwd(old, oa, r), lambda: bwd(new, ob, r))
+                opt('gn_resident', 192)
+                del x, dy, r, oa, ob
+            for M, C in ((262144, 320), (65536, 640), (16384, 1280)):
+                x, dy, gamma, beta = rnd(M, C, dtype=BF), rnd(M, C, dtype=BF), 1 + 0.25 * rnd(C), rnd(C)
+                oa, ob = (ln_bufs(M, C, None) for _ in libs)
+                label = f'{M}x{C} pass {rep}'
+                row('ln_fwd', label, lambda: ok(ln_fwd(old, oa, x, gamma, beta, M, C)), lambda: ok(ln_fwd(new, ob, x, gamma, beta, M, C)))
+                row('ln_bwd', label, lambda: ok(ln_bwd(old, oa, x, dy, None, gamma, M, C)), lambda: ok(ln_bwd(new, ob, x, dy, None, gamma, M, C)))
+                ca, cb = (dict(out=sent(C), scratch=sent(256 * C * 2)) for _ in libs)
+                row('colsum_accum', label, lambda: ok(colsum(old, ca, x, M, C)), lambda: ok(colsum(new, cb, x, M, C)))
+                del x, dy, oa, ob
+            for B, HW, C in ((256, 1024, 320), (256, 64, 1280)):
+                x = rnd(B * HW, C, dtype=BF)
+                oa, ob = (dict(out=sent(B, C, dtype=BF), db=sent(C), scratch=sent(int(new.da_norm_scratch_floats(B, HW, C)))) for _ in libs)
+                row('image_colsum', f'B={B} HW={HW} C={C} pass {rep}', lambda: ok(image_colsum(old, oa, x, B, HW, C)),
+                    lambda: ok(image_colsum(new, ob, x, B, HW, C)))
+                del x
+        for op, pcts in spread.items():
+            med = sorted(pcts)[len(pcts) // 2]
+            print(f'norms spread {op:20s}: median {med:+5.1f} %, rows {min(pcts):+5.1f} ... {max(pcts):+5.1f} % ({len(pcts)} rows)', flush=True)
 
 
 if __name__ == '__main__':
