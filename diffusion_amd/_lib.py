@@ -66,6 +66,12 @@ SIGNATURES = {
     'da_image_resize': [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp],
     'da_clip_preprocess': [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _fp, _fp, _vp, _i, _vp],
     'da_clip_score': [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _vp],
+    'da_conv2d_relu_fwd': [_vp, _l, _vp, _fp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    'da_conv2d_tile_for': [_i],
+    'da_pool2d_fwd': [_vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    'da_avgpool_global_f32': [_vp, _l, _fp, _l, _i, _i, _i, _vp],
+    'da_inception_preprocess': [_vp, _i, _i, _i, _i, _vp, _vp],
+    'da_feature_moments': [_fp, _l, _i, _i, _vp, _vp, _vp, _vp],
     'da_sampler_step': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_ms': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],

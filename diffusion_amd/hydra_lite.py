@@ -27,6 +27,8 @@ TARGET_ALIASES = {
     'torchmetrics.MeanSquaredError': 'diffusion_amd.models.composer_shim.MeanSquaredError',
     'torchmetrics.multimodal.clip_score.CLIPScore': 'diffusion_amd.metrics.clip_score.CLIPScore',
     'torchmetrics.multimodal.CLIPScore': 'diffusion_amd.metrics.clip_score.CLIPScore',
+    'torchmetrics.image.fid.FrechetInceptionDistance': 'diffusion_amd.metrics.fid.FrechetInceptionDistance',
+    'torchmetrics.image.FrechetInceptionDistance': 'diffusion_amd.metrics.fid.FrechetInceptionDistance',
     'torch.optim.AdamW': 'diffusion_amd.optim.FusedAdamW',
 }
 TARGET_PREFIX_ALIASES = [

@@ -645,6 +645,99 @@ def clip_score(img, txt, scores, state):
               _vec(scores, B, 'scores'), _vec(state, 2, 'state'), _stream())
 
 
+INCEPTION_SIDE = 299   # da_inception_preprocess: the FID Inception's input side
+
+
+def conv2d_tile_for(Cout: int) -> int:
+    """the column tile (32 / 64 / 96) ``da_conv2d_relu_fwd`` picks for ``Cout``"""
+    return int(_lib.load().da_conv2d_tile_for(int(Cout)))
+
+
+def conv2d_relu_fwd(X, W, bias, Y, B, Hin, Win, kh, kw, stride=1, ph=0, pw=0, relu=True, tile_n=0):
+    """``da_conv2d_relu_fwd``: Y[B*Hout*Wout, Cout] = act(conv(X[B*Hin*Win, Cin], W[Cout, kh*kw*Cin]) + bias).  X and Y are
+    bf16 device matrices with unit column stride (column slices of wider buffers are fine), W contiguous bf16 in
+    [Cout][kh][kw][Cin] order, bias fp32 [Cout] or None.  Returns (Hout, Wout)."""
+    Cin, Cout = X.shape[1], Y.shape[1]
+    if Hin + 2 * ph < kh or Win + 2 * pw < kw:
+        raise ValueError(f'conv2d_relu_fwd: a {kh}x{kw} window does not fit {Hin}x{Win} padded by ({ph}, {pw})')
+    Hout, Wout = (Hin + 2 * ph - kh) // stride + 1, (Win + 2 * pw - kw) // stride + 1
+    if X.shape[0] != B * Hin * Win or Y.shape[0] != B * Hout * Wout:
+        raise ValueError(f'conv2d_relu_fwd: X has {X.shape[0]} rows, Y {Y.shape[0]}; need {B * Hin * Win} and '
+                         f'{B * Hout * Wout}')
+    if W.dim() != 2 or W.dtype != BF16 or not W.is_cuda or not W.is_contiguous() or tuple(W.shape) != (Cout, kh * kw * Cin) \
+            or W.data_ptr() % 16:
+        raise ValueError(f'conv2d_relu_fwd: W must be contiguous bf16 [{Cout}, {kh * kw * Cin}] on the device, 16-byte aligned')
+    px, ldx = _mat(X, name='X')
+    py, ldy = _mat(Y, name='Y')
+    pb = _vec(bias, Cout, 'bias')
+    if pb % 16:
+        raise ValueError('conv2d_relu_fwd: bias must be 16-byte aligned')
+    with _Timed('conv_rect', 2.0 * B * Hout * Wout * Cout * kh * kw * Cin):
+        _lib.call('da_conv2d_relu_fwd', px, ldx, W.data_ptr(), pb, py, ldy, B, Hin, Win, Hout, Wout, Cin, Cout, kh, kw,
+                  int(stride), int(ph), int(pw), int(bool(relu)), int(tile_n), _stream())
+    return Hout, Wout
+
+
+def pool2d_fwd(X, Y, B, Hin, Win, stride, pad, kind):
+    """``da_pool2d_fwd``: 3x3 max (kind 0) or average over the in-bounds taps (kind 1) of bf16 NHWC rows.  Returns
+    (Hout, Wout)."""
+    C = X.shape[1]
+    if Hin + 2 * pad < 3 or Win + 2 * pad < 3:
+        raise ValueError(f'pool2d_fwd: a 3x3 window does not fit {Hin}x{Win} padded by {pad}')
+    Hout, Wout = (Hin + 2 * pad - 3) // stride + 1, (Win + 2 * pad - 3) // stride + 1
+    if X.shape[0] != B * Hin * Win or tuple(Y.shape) != (B * Hout * Wout, C):
+        raise ValueError(f'pool2d_fwd: X {tuple(X.shape)}, Y {tuple(Y.shape)}; need [{B * Hin * Win}, C] and '
+                         f'[{B * Hout * Wout}, C]')
+    px, ldx = _mat(X, name='X')
+    py, ldy = _mat(Y, name='Y')
+    _lib.call('da_pool2d_fwd', px, ldx, py, ldy, B, Hin, Win, Hout, Wout, C, int(stride), int(pad), int(kind), _stream())
+    return Hout, Wout
+
+
+def avgpool_global_f32(X, out, B, HW):
+    """``da_avgpool_global_f32``: out[b, c] = mean over the HW rows of image b; X bf16 [B*HW, C], out fp32 [B, C]."""
+    C = X.shape[1]
+    if X.shape[0] != B * HW or out.dim() != 2 or tuple(out.shape) != (B, C) or out.dtype != F32 or not out.is_cuda \
+            or out.stride(1) != 1:
+        raise ValueError(f'avgpool_global_f32: X {tuple(X.shape)}, out {tuple(out.shape)} {out.dtype}')
+    px, ldx = _mat(X, name='X')
+    _lib.call('da_avgpool_global_f32', px, ldx, out.data_ptr(), max(out.stride(0), C), B, HW, C, _stream())
+    return out
+
+
+def inception_preprocess(images, out):
+    """``da_inception_preprocess``: planar [B, 3, H, W] device images, uint8 levels or fp32 in [0, 1], through the TF1-style
+    bilinear resize to 299 x 299 and (v - 128) / 128 into out bf16 [B * 299 * 299, 8] (channels 3..7 zero)."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.uint8, F32) \
+            or images.dim() != 4 or images.shape[1] != 3 or not images.is_contiguous() or images.shape[0] < 1:
+        raise ValueError('inception_preprocess: images must be a contiguous uint8 or fp32 [B, 3, H, W] device tensor')
+    B, _, H, W = images.shape
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError('inception_preprocess: image sides must be in 1..65535')
+    n = B * INCEPTION_SIDE * INCEPTION_SIDE
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != BF16 or not out.is_contiguous() \
+            or tuple(out.shape) != (n, 8) or out.data_ptr() % 16:
+        raise ValueError(f'inception_preprocess: out must be a contiguous bf16 [{n}, 8] device tensor, 16-byte aligned')
+    _lib.call('da_inception_preprocess', images.data_ptr(), int(images.dtype == F32), B, H, W, out.data_ptr(), _stream())
+    return out
+
+
+def feature_moments(F, fsum, cov, n):
+    """``da_feature_moments``: fsum[d] += sum_b F[b, d], cov[d, e] += sum_b F[b, d] F[b, e], n[0] += B.  F fp32 [B, D] with
+    unit column stride; fsum [D], cov [D, D], n [1]: contiguous float64 device tensors."""
+    if F.dim() != 2 or F.dtype != F32 or not F.is_cuda or F.stride(1) != 1 or F.shape[0] < 1:
+        raise ValueError('feature_moments: F must be an fp32 [B, D] device matrix with unit column stride')
+    B, D = F.shape
+    ldf = max(F.stride(0), D)
+    if D % 8 or ldf % 4 or F.data_ptr() % 16:
+        raise ValueError('feature_moments: D % 8 == 0, row stride % 4 == 0 and a 16-byte aligned base are required')
+    for z, shape, nm in ((fsum, (D,), 'sum'), (cov, (D, D), 'cov'), (n, (1,), 'n')):
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.float64 or not z.is_cuda or not z.is_contiguous() \
+                or tuple(z.shape) != shape:
+            raise ValueError(f'feature_moments: {nm} must be a contiguous float64 device tensor {shape}')
+    _lib.call('da_feature_moments', F.data_ptr(), ldf, B, D, fsum.data_ptr(), cov.data_ptr(), n.data_ptr(), _stream())
+
+
 def _rescale_operands(fn, factor, HW, npix):
     """``factor=`` / ``HW=`` of the four step wrappers (guidance rescale): the sample's pixel count, checked."""
     if HW is None or int(HW) < 1 or npix % int(HW):

@@ -379,8 +379,9 @@ class Trainer:
         metric states are summed over the ranks (squared-error sum and count, as torchmetrics' dist_reduce_fx="sum" does) and
         logged as ``metrics/eval/<name>``.  A ``CLIPScore`` among the validation metrics (metrics/clip_score.py) is fed the
         images ``eval_forward`` generates per entry of ``val_guidance_scales`` and reduces its own two-float state over the
-        ranks in ``compute()``; FID / Inception score need a network whose op set is not on the HIP path and stay out of
-        scope.  Callbacks get ``eval_batch_end`` after each batch's metric updates.  Nothing collective runs before the final
+        ranks in ``compute()``; a ``FrechetInceptionDistance`` (metrics/fid.py) is fed the batch's real images and the
+        generated ones per guidance scale and reduces its float64 feature moments the same way (the Inception score stays out
+        of scope).  Callbacks get ``eval_batch_end`` after each batch's metric updates.  Nothing collective runs before the final
         reduction, so the ranks may see different numbers of batches (the COCO loader's unpadded partition).  With no eval
         dataloader this returns {}."""
         if self.eval_dataloader is None:

@@ -478,6 +478,50 @@ int da_clip_preprocess(const unsigned char* src, int B, int H, int W, int R, int
 int da_clip_score(const float* img, long ldi, const float* txt, long ldt, int B, int D, float* scores, float* state,
                   da_stream_t stream);
 
+/* ---- the FID metric: Inception-v3 tower (models/inception_hip.py) and float64 feature moments (metrics/fid.py) ----
+ *
+ * Convolution + folded BatchNorm + ReLU of the FID Inception network (torch-fidelity's FeatureExtractorInceptionV3: every
+ * BasicConv2d is F.relu(bn(conv(x))), eps 1e-3; the BatchNorm is folded into W and bias at load time):
+ *   Y[b, oh, ow, n] = act(bias[n] + sum_{i < kh, j < kw, c < Cin} X[b, oh s - ph + i, ow s - pw + j, c] W[n][i][j][c])
+ * X: bf16 NHWC rows of ldx elements, Y: bf16 rows of ldy >= Cout elements (a branch writes its column slice of the block's
+ * concat buffer, which replaces torch.cat), W: bf16 [Cout][kh][kw][Cin] contiguous, bias: fp32 [Cout] or NULL.  bf16 MFMA
+ * with fp32 accumulation over k = (i, j, c) in that order, + bias in fp32, ReLU if relu = 1, one RNE rounding to bf16.
+ * kh, kw in 1..7, stride 1 or 2, ph, pw in 0..3, Cin % 8 == 0, Cout % 8 == 0, ldx % 8 == 0, ldy % 8 == 0; X, W, Y and
+ * bias 16-byte aligned.  Hout and Wout must equal (Hin + 2 ph - kh) / s + 1 and (Win + 2 pw - kw) / s + 1 (floor; the
+ * padded image must hold one window).  tile_n: 0 takes the column tile da_conv2d_tile_for(Cout) picks, 32 / 64 / 96
+ * force one (the summation order of an output element does not depend on the tile).  No workspace, no host synchronisation.  DA_ERR_SHAPE (nothing launched) for anything else, and for
+ * B Hout Wout or B Hin Win >= 2^31. */
+int da_conv2d_relu_fwd(const void* X, long ldx, const void* W, const float* bias, void* Y, long ldy, int B, int Hin,
+                       int Win, int Hout, int Wout, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw,
+                       int relu, int tile_n, da_stream_t stream);
+/* the column tile (32, 64 or 96) da_conv2d_relu_fwd uses for Cout at tile_n = 0; 0 for a Cout it rejects */
+int da_conv2d_tile_for(int Cout);
+
+/* F.max_pool2d(x, 3, stride) (kind 0) and F.avg_pool2d(x, 3, stride, padding, count_include_pad=False) (kind 1) on bf16
+ * NHWC rows: stride 1 or 2, pad 0 or 1, C % 8 == 0, ldx, ldy >= C and multiples of 8, Hout = (Hin + 2 pad - 3) / s + 1.
+ * The average is the fp32 sum of the in-bounds taps in row-major tap order, one fp32 DIVISION by their count (not a
+ * reciprocal multiply), one RNE rounding to bf16.  The maximum ignores taps outside the image. */
+int da_pool2d_fwd(const void* X, long ldx, void* Y, long ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
+                  int stride, int pad, int kind, da_stream_t stream);
+
+/* F.adaptive_avg_pool2d(x, 1) of bf16 NHWC rows into fp32: out[b][c] = (sum over the HW rows of image b, in row order,
+ * fp32) / HW.  out rows of ldo >= C floats. */
+int da_avgpool_global_f32(const void* X, long ldx, float* out, long ldo, int B, int HW, int C, da_stream_t stream);
+
+/* The input transform of the FID Inception (torch-fidelity: interpolate_bilinear_2d_like_tensorflow1x(x, (299, 299),
+ * align_corners=False), then (x - 128) / 128) of planar images src [B, 3, H, W]: src_kind 0 uint8 levels, 1 fp32 in [0, 1]
+ * turned into levels by floor(clamp(255 x, 0, 255)) (torchmetrics normalize=True: (x * 255).byte()).  Per axis
+ * scale = float(in / 299), src = dst * scale in fp32 (no half-pixel offset), lo = floor(src), hi = min(lo + 1, in - 1);
+ * fp32 lerp lo + (hi - lo) * frac along x on both rows, then along y; no antialiasing.  This is NOT da_image_resize's
+ * filter.  out: bf16 [B * 299 * 299][8] NHWC, channels 3..7 zero, 16-byte aligned. */
+int da_inception_preprocess(const void* src, int src_kind, int B, int H, int W, void* out, da_stream_t stream);
+
+/* torchmetrics' FID state update on fp32 features F [B][D] (rows of ldf floats, ldf % 4 == 0, 16-byte aligned):
+ * sum[d] += sum_b F[b][d], cov[d][e] += sum_b F[b][d] F[b][e], n[0] += B, all float64 in device memory (sum [D], cov
+ * [D][D], n [1]).  Every output element is owned by one thread that adds the batch in index order to the stored value:
+ * no atomics, identical bits run to run.  D % 8 == 0, D <= 16384. */
+int da_feature_moments(const float* F, long ldf, int B, int D, double* sum, double* cov, double* n, da_stream_t stream);
+
 int da_cast_f32_bf16(const float* src, void* dst, long n, da_stream_t stream);
 
 /* dst[c][T-1-t][n] = src[n][t][c]: the weight layout da_gemm_nt needs for dgrad */
