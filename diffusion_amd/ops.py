@@ -190,6 +190,10 @@ def gemm_nt_geglu(A, W, F, G, bias):
         raise ValueError('gemm_nt_geglu: shape mismatch')
     if not geglu_fusable(inner, K):
         raise ValueError(f'gemm_nt_geglu needs inner % 160 == 0 and K % 64 == 0, got {inner}, {K}')
+    if M * lda * 2 >= 1 << 32:   # the fused kernel addresses A by 32-bit byte offsets (DA_ERR_SHAPE): two launches, same bits
+        gemm_nt(A, W, F, Geom.linear(M), bias=bias)
+        geglu_fwd(F, G)
+        return
     with _Timed('gemm_nt2_kernel<4,5,4,4>', 2.0 * M * 2 * inner * K, (M, 2 * inner, K, 1, 'geglu')):
         _lib.call('da_gemm_nt_geglu', a_ptr, lda, w_ptr, f_ptr, ldf, g_ptr, ldg, _vec(bias, 2 * inner, 'bias'), M, inner,
                   K, _stream())
@@ -211,6 +215,11 @@ def gemm_nt_geglu_bwd(dY, Wt, F, dF):
         raise ValueError('gemm_nt_geglu_bwd: shape mismatch')
     if not geglu_bwd_fusable(inner, K):
         raise ValueError(f'gemm_nt_geglu_bwd needs inner % 320 == 0 and K % 64 == 0, got {inner}, {K}')
+    if M * lddy * 2 >= 1 << 32:   # as in gemm_nt_geglu: the product goes through HBM once, then da_geglu_bwd
+        dG = torch.empty(M, inner, device=dY.device, dtype=BF16)
+        gemm_nt(dY, Wt, dG, Geom.linear(M))
+        geglu_bwd(F, dG, dF)
+        return
     with _Timed('gemm_nt2_kernel<4,5,4,4>', 2.0 * M * inner * K, (M, inner, K, 1, 'geglu_bwd')):
         _lib.call('da_gemm_nt_geglu_bwd', dy_ptr, lddy, w_ptr, f_ptr, ldf, df_ptr, lddf, M, inner, K, _stream())
 

@@ -306,6 +306,58 @@ def test_linear_input_of_4_gib_takes_the_pointer_form(ops, dev):
         check_blocks(out[lo:lo + 512], ref, what=f'rows {lo}..')
 
 
+def _encoder_level_input(B, dev):
+    """[B * 65536, 128] bf16, the first level of the VAE encoder at 256 px (4 GiB at B = 256), filled in slices"""
+    M = B << 16
+    A = torch.empty(M, 128, device=dev, dtype=BF)
+    for lo in range(0, M, 1 << 20):
+        hi = min(M, lo + (1 << 20))
+        A[lo:hi] = rnd(hi - lo, 128, dev=dev, seed=lo >> 20).to(BF)
+    return A
+
+
+ENCODER_IMAGES = (0, 127, 128, -1)   # the first, the two either side of the 2 GiB mark, the last (past 4 GiB - 16 MiB)
+
+
+@pytest.mark.parametrize('B', [256, 255])
+def test_encoder_conv_at_4_gib(ops, dev, B):
+    """VAEEncoderHIP.moments_nhwc8 encodes the whole batch at once: at the pipeline's per-GPU batch of 256 at 256 px every
+    128-channel activation of the first level is [2^24, 128] bf16, exactly 4 GiB - where the direct-epilogue guard of the
+    384 x 128 form flips to the strip epilogue (M * ldc * 2 < 2^32); B = 255 sits just under it and stores directly."""
+    H, C = 256, 128
+    M = B * H * H
+    A = _encoder_level_input(B, dev)
+    w = rnd(C, 9 * C, dev=dev, seed=2, scale=(9 * C)**-0.5).to(BF)
+    bias = rnd(C, dev=dev, seed=3)
+    assert nt_variant(ops, M, C, 9 * C, C) == 18
+    out = torch.empty(M, C, device=dev, dtype=BF)
+    ops.gemm_nt(A, w, out, ops.Geom.conv(B, H, H), bias=bias)
+    for b in ENCODER_IMAGES:
+        lo = (b % B) * H * H
+        ref = conv3x3_ref(A[lo:lo + H * H], w, 1, H, H) + bias
+        check_blocks(out[lo:lo + H * H], ref, what=f'conv 128->128 at batch {B}, image {b % B}')
+
+
+def test_encoder_groupnorm_at_4_gib(ops, dev):
+    """GroupNorm + SiLU of the same [2^24, 128] activation: image bases up to 4 GiB - 16 MiB, each image against fp32 torch"""
+    B, HW, C, G, eps = 256, 65536, 128, 32, 1e-6
+    x = _encoder_level_input(B, dev)
+    gamma = rnd(C, dev=dev, seed=2) * 0.2 + 1.0
+    beta = rnd(C, dev=dev, seed=3) * 0.2
+    y = torch.empty_like(x)
+    st = torch.empty(B * G * 2, device=dev)
+    ss = torch.empty(B * C * 2, device=dev)
+    scratch = torch.empty(ops.norm_scratch_floats(B, HW, C), device=dev)
+    ops.groupnorm_fwd(x, y, gamma, beta, st, ss, scratch, B, HW, C, G, eps, 1)
+    for b in ENCODER_IMAGES:
+        lo = (b % B) * HW
+        xf = x[lo:lo + HW].float().reshape(1, HW, G, C // G)
+        mean = xf.mean(dim=(1, 3), keepdim=True)
+        var = xf.var(dim=(1, 3), unbiased=False, keepdim=True)
+        n = ((xf - mean) * torch.rsqrt(var + eps)).reshape(HW, C) * gamma + beta
+        check_blocks(y[lo:lo + HW], F.silu(n), what=f'groupnorm+silu, image {b % B}')
+
+
 def _record(case, **kv):
     import os
     import sys
