@@ -82,6 +82,8 @@ SIGNATURES = {
     'da_sampler_step_ms_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_blend_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_ms_blend_rs': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
+    'da_randn_philox': [_vp, C.c_uint, C.c_uint, _fp, _i, _i, _i, _i, _i, _vp],
+    'da_sampler_step_rng': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _vp, _l, _i, _i, _i, _i, _i, _vp],
     'da_mse_loss_w': [_fp, _fp, _vp, _fp, _fp, _l, _i, _i, _ll, _fp, _i, _f, _f, _i, _vp],
     'da_mse_loss': [_fp, _fp, _vp, _fp, _fp, _l, _f, _f, _i, _vp],
     'da_mse_loss_c': [_fp, _fp, _vp, _fp, _fp, _l, _i, _f, _f, _i, _vp],

@@ -15,8 +15,12 @@
 // ONE kernel body (sampler_step_kernel<MS, BLEND, RS>) and ONE host path (step<MS, BLEND, RS>: the argument rules and the
 // launch).  What a form does not use is an empty operand struct and code under `if constexpr`, so the plain instantiations
 // are the kernels they were before the other forms existed.
+// A ninth entry, da_sampler_step_rng, is any of the eight forms with the noise term drawn inside the kernel (RNG: philox.hpp,
+// keyed by the image's seed, the step's draw number and the pixel), so a stochastic step is one launch, can sit in a captured
+// graph (the draw number is device data like the coefficients) and gives an image the same noise in any batch.
 #include "common.hpp"
 #include "diffusion_amd.h"
+#include "philox.hpp"
 
 namespace {
 
@@ -61,6 +65,25 @@ struct Form<true> {
   float* hist;
 };
 
+// The in-kernel draw: one uint64 seed per sample, and HW, the sample's pixel count (a pixel's counter is its index in its
+// own image).  The row of an RNG form is wider: first order {cx, cm, cn, guidance, bA, bS, draw, 0}, two-step {ax, am, kx, k0,
+// k1, guidance, bA, bS, kn, draw, 0, 0}; draw is a uint32 bit pattern in a float slot.
+template <bool RNG>
+struct Rng {
+  const uint64_t* seeds;
+  int HW;
+};
+template <>
+struct Rng<false> {};  // the eight entries without it: the operand list and the code they always had
+
+// v + k z with the product and the sum each rounded: the two-step forms' noise term is defined as the torch expression
+// x += kn * z on the deterministic update, so it must not contract into an FMA
+__device__ __forceinline__ float add_scaled_unfused(float v, float k, float z) {
+#pragma clang fp contract(off)
+  const float kz = k * z;
+  return v + kz;
+}
+
 // The step, every form of it.  First order (MS = false), coef = {cx, cm, cn, guidance} and, BLEND, {bA, bS, 0, 0} after it:
 //   m     = cfg ? pu + g (pt - pu) : p
 //   v     = cx x + cm m (+ cn z)
@@ -72,16 +95,28 @@ struct Form<true> {
 //   v     = kx x + k0 d (+ k1 hist)             k1 == 0 (a first-order step): hist is not read, it may hold anything
 //   hist  = d
 // k1 comes from device memory like the rest, so one captured launch serves first- and second-order steps alike.
+// RNG (any form): z is philox::normals(seed of the pixel's sample, pixel in the sample, draw, stream 0) and
+//   v    += cn z  (first order: what the noise operand does)      v = v + kn z  (two-step: add_scaled_unfused)
+// drawn iff the coefficient is not 0, which is uniform across the launch; hist keeps the noise-free data prediction.
 // Every form: RS multiplies m by the sample's factor first, BLEND replaces v by m v + (1 - m) kn last, and
 //   x_out = v,  xt = bf16(v)                    channels C..7 of x_out, xt and hist exactly 0
 // every load of a pixel comes before its first store, and a pixel is read and written by one thread only: x_out may be x
-template <bool MS, bool BLEND, bool RS>
-__global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
+template <bool MS, bool BLEND, bool RS, bool RNG = false>
+__global__ void __launch_bounds__((BLEND || RS || RNG) ? SMP_BLOCK : SMP_MAX_BLOCK)
     sampler_step_kernel(const float* pred, const float* x, Form<MS> fm, const float* coef, float* x_out, bf16* xt_out,
-                        long npix, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs) {
+                        long npix, int C, int cfg, int copies, Blend<BLEND> bl, Rescale<RS> rs, Rng<RNG> rg) {
   const f32x4 ka = *reinterpret_cast<const f32x4*>(coef);
-  f32x4 kb = {0, 0, 0, 0};  // the second half of the row: the first-order form has (and reads) one only when blended
-  if constexpr (MS || BLEND) kb = *reinterpret_cast<const f32x4*>(coef + 4);
+  f32x4 kb = {0, 0, 0, 0};  // the second half of the row: the first-order form has (and reads) one only when blended or RNG
+  if constexpr (MS || BLEND || RNG) kb = *reinterpret_cast<const f32x4*>(coef + 4);
+  float kn_z = 0.f;     // the noise coefficient of an RNG form and its draw number, bit-cast after the vector load
+  uint32_t draw = 0;
+  if constexpr (RNG && MS) {
+    const f32x4 kc = *reinterpret_cast<const f32x4*>(coef + 8);
+    kn_z = kc[0], draw = __float_as_uint(kc[1]);
+  } else if constexpr (RNG) {
+    kn_z = ka[2], draw = __float_as_uint(kb[2]);
+  }
+  const bool draws = RNG && kn_z != 0.0f;  // uniform across the launch
   const float c0 = ka[0], c1 = ka[1];  // {cx, cm} or {ax, am}
   const float cn = ka[2], kx = ka[2], k0 = ka[3], k1 = kb[0];
   const float g = MS ? kb[1] : ka[3], bA = MS ? kb[2] : kb[0], bS = MS ? kb[3] : kb[1];
@@ -112,12 +147,22 @@ __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
     }
     long b = 0;
     int pix = 0;
-    if constexpr (!MS) {  // where the pixel's noise draw is
+    if constexpr (!MS && !RNG) {  // where the pixel's noise draw is
       b = i / fm.HW;
       pix = (int)(i - b * fm.HW);
     }
     float fac = 1.f;
     if constexpr (RS) fac = rs.factor[i / rs.hw];
+    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (RNG) {
+      if (draws) {
+        const long bz = i / rg.HW;
+        const uint32_t pz = (uint32_t)(i - bz * rg.HW);
+        const uint64_t seed = rg.seeds[bz];
+        philox::normals(seed, pz, draw, 0u, 0u, z);
+        if (C > 4) philox::normals(seed, pz, draw, 0u, 1u, z + 4);  // uniform
+      }
+    }
     float o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -134,6 +179,11 @@ __global__ void __launch_bounds__((BLEND || RS) ? SMP_BLOCK : SMP_MAX_BLOCK)
         if constexpr (MS) {
           v = kx * xv + k0 * dv;
           if (second) v += k1 * (c < 4 ? h0[c & 3] : h1[c & 3]);
+          if constexpr (RNG) {
+            if (draws) v = add_scaled_unfused(v, kn_z, z[c]);
+          }
+        } else if constexpr (RNG) {
+          if (draws) v += cn * z[c];
         } else {
           if (fm.noise) v += cn * fm.noise[(b * C + c) * fm.HW + pix];
         }
@@ -286,10 +336,11 @@ struct StepArgs {
   float* hist = nullptr;         // two-step
   const float *known8 = nullptr, *eps8 = nullptr, *mask = nullptr;  // BLEND
   const float* factor = nullptr;                                    // RS
+  const uint64_t* seeds = nullptr;                                  // RNG
 };
 
 // The argument rules of every step entry, each stated once, and the launch.
-template <bool MS, bool BLEND, bool RS>
+template <bool MS, bool BLEND, bool RS, bool RNG = false>
 int step(const StepArgs& a) {
   // shapes; the two-step forms check HW like the rest, though only their RS forms read it
   if (a.npix <= 0 || a.HW <= 0 || (a.npix % a.HW) || a.C < 1 || a.C > 8 || (a.copies != 1 && a.copies != 2))
@@ -299,10 +350,11 @@ int step(const StepArgs& a) {
   if (MS && !a.hist) return DA_ERR_SHAPE;
   if (BLEND && (!a.known8 || !a.eps8 || !a.mask)) return DA_ERR_SHAPE;
   if (RS && !a.factor) return DA_ERR_SHAPE;
-  // alignment: 16 bytes for every pointer given (the optional ones included), 4 for factor
+  if (RNG && !a.seeds) return DA_ERR_SHAPE;
+  // alignment: 16 bytes for every pointer given (the optional ones included), 4 for factor, 8 for seeds
   const uintptr_t ptrs = (uintptr_t)a.pred | (uintptr_t)a.x | (uintptr_t)a.coef | (uintptr_t)a.x_out | (uintptr_t)a.xt_out |
                          (uintptr_t)a.noise | (uintptr_t)a.hist | (uintptr_t)a.known8 | (uintptr_t)a.eps8 | (uintptr_t)a.mask;
-  if ((ptrs & 15) || ((uintptr_t)a.factor & 3)) return DA_ERR_SHAPE;
+  if ((ptrs & 15) || ((uintptr_t)a.factor & 3) || ((uintptr_t)a.seeds & 7)) return DA_ERR_SHAPE;
   Form<MS> fm;
   if constexpr (MS) fm = {a.hist};
   else fm = {a.noise, a.HW};
@@ -310,13 +362,80 @@ int step(const StepArgs& a) {
   if constexpr (BLEND) bl = {a.known8, a.eps8, a.mask};
   Rescale<RS> rs;
   if constexpr (RS) rs = {a.factor, a.HW};
-  hipLaunchKernelGGL((sampler_step_kernel<MS, BLEND, RS>), dim3(pixel_grid(a.npix)), dim3(SMP_BLOCK), 0, a.s, a.pred, a.x,
-                     fm, a.coef, a.x_out, (bf16*)a.xt_out, a.npix, a.C, a.cfg ? 1 : 0, a.copies, bl, rs);
+  Rng<RNG> rg;
+  if constexpr (RNG) rg = {a.seeds, a.HW};
+  hipLaunchKernelGGL((sampler_step_kernel<MS, BLEND, RS, RNG>), dim3(pixel_grid(a.npix)), dim3(SMP_BLOCK), 0, a.s, a.pred,
+                     a.x, fm, a.coef, a.x_out, (bf16*)a.xt_out, a.npix, a.C, a.cfg ? 1 : 0, a.copies, bl, rs, rg);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
 
+// da_randn_philox: one work item per (sample, pixel, channel block), NCHW stores (coalesced along the pixels of a channel)
+__global__ void __launch_bounds__(SMP_BLOCK)
+    randn_philox_kernel(const uint64_t* seeds, uint32_t draw, uint32_t stream, float* out, long nitem, int nblk, int C, int HW,
+                        int kind) {
+  GRID_STRIDE(i, nitem) {
+    const long bk = i / HW;  // sample * nblk + block
+    const uint32_t pix = (uint32_t)(i - bk * HW);
+    const long b = bk / nblk;
+    const uint32_t blk = (uint32_t)(bk - b * nblk);
+    const uint64_t seed = seeds[b];
+    float z[4];
+    if (kind == 0) {  // uniform
+      philox::normals(seed, pix, draw, stream, blk, z);
+    } else {
+      uint32_t r[4];
+      philox::words(pix, draw, stream, blk, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) z[j] = __uint_as_float(r[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = (int)blk * 4 + j;
+      if (c < C) out[(b * C + c) * HW + pix] = z[j];
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int da_randn_philox(const unsigned long long* seeds, unsigned draw, unsigned stream, float* out, int B, int C,
+                               int H, int W, int kind, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B <= 0 || H <= 0 || W <= 0 || C < 1 || C > 8 || (long)H * W > 0x7fffffffL) return DA_ERR_SHAPE;
+  if (stream > 1u || (kind != 0 && kind != 1) || (kind == 1 && (C % 4))) return DA_ERR_SHAPE;
+  if (!seeds || !out || ((uintptr_t)seeds & 7) || ((uintptr_t)out & 15)) return DA_ERR_SHAPE;
+  const int nblk = (C + 3) / 4, HW = H * W;
+  const long nitem = (long)B * nblk * HW;
+  hipLaunchKernelGGL(randn_philox_kernel, dim3(pixel_grid(nitem)), dim3(SMP_BLOCK), 0, s,
+                     reinterpret_cast<const uint64_t*>(seeds), (uint32_t)draw, (uint32_t)stream, out, nitem, nblk, C, HW, kind);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// ---- the stochastic step: one entry, the form as a mask, the same StepArgs and step<...> with RNG on
+extern "C" int da_sampler_step_rng(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
+                                   const float* eps8, const float* mask, const float* factor,
+                                   const unsigned long long* seeds, float* x_out, void* xt_out, long npix, int HW, int C,
+                                   int form, int cfg, int copies, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (form < 0 || form > 7) return DA_ERR_SHAPE;
+  StepArgs a{pred, x, coef, x_out, xt_out, npix, HW, C, cfg, copies, s};
+  a.seeds = reinterpret_cast<const uint64_t*>(seeds);
+  if (form & 1) a.hist = hist;
+  if (form & 2) a.known8 = known8, a.eps8 = eps8, a.mask = mask;
+  if (form & 4) a.factor = factor;
+  switch (form) {
+    case 0: return step<false, false, false, true>(a);
+    case 1: return step<true, false, false, true>(a);
+    case 2: return step<false, true, false, true>(a);
+    case 3: return step<true, true, false, true>(a);
+    case 4: return step<false, false, true, true>(a);
+    case 5: return step<true, false, true, true>(a);
+    case 6: return step<false, true, true, true>(a);
+    default: return step<true, true, true, true>(a);
+  }
+}
 
 // ---- the eight step entries: the call's operands into a StepArgs, then step<MS, BLEND, RS>
 extern "C" int da_sampler_step(const float* pred, const float* x, const float* noise, const float* coef, float* x_out,

@@ -26,7 +26,8 @@ from ..schedulers.schedulers import ContinuousTimeScheduler
 from .pixel_diffusion import PixelDiffusion
 from ..sampling import check_guidance_rescale
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
-                         check_inference_scheduler, check_snr_gamma, check_timestep_spacing, make_inference_scheduler)
+                         check_eta, check_inference_scheduler, check_snr_gamma, check_timestep_spacing,
+                         make_inference_scheduler)
 from .stable_diffusion import StableDiffusion
 from .unet import UNetConfig, UNetHIP
 
@@ -100,6 +101,15 @@ def _check_zero_snr_options(zero_terminal_snr, prediction_type, timestep_spacing
     return check_timestep_spacing(timestep_spacing)
 
 
+def _check_inference_eta(inference_eta, inference_scheduler) -> float:
+    """``inference_eta=`` of the factories: a number in [0, 1], and 0 unless the solver is DDIM.  Host only."""
+    inference_eta = check_eta(inference_eta)
+    if inference_eta and inference_scheduler != 'ddim':
+        raise ValueError(f'inference_eta = {inference_eta} is the DDIM sampler\'s parameter: inference_scheduler '
+                         f'{inference_scheduler!r} has none')
+    return inference_eta
+
+
 def stable_diffusion_2(
     model_name: str = 'stabilityai/stable-diffusion-2-base',
     pretrained: bool = True,
@@ -119,9 +129,13 @@ def stable_diffusion_2(
     snr_gamma: Optional[float] = None,
     timestep_spacing: Optional[str] = None,
     guidance_rescale: float = 0.0,
+    inference_eta: float = 0.0,
 ):
-    """``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's)
-    or ``'dpm++2m'`` (``DPMSolverMultistepScheduler``).
+    """``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's),
+    ``'dpm++2m'`` (``DPMSolverMultistepScheduler``) or ``'dpm++2m-sde'`` (its SDE form: noise in every step).
+    ``inference_eta``: the DDIM sampler's eta in [0, 1] (``ValueError`` above 0 with another solver); above 0 the sampler
+    is stochastic, 1 is DDPM ancestral sampling.  ``eval_forward``, the image metrics and the image logger follow both, with
+    ``val_seed`` as the base of the per-image seeds.
 
     ``zero_terminal_snr``: both schedulers rescale their betas so that the last timestep is pure noise (Lin et al.,
     arXiv:2305.08891; ``rescale_betas_zero_snr``); needs a v-prediction U-Net config.  ``timestep_spacing``: the inference
@@ -129,6 +143,7 @@ def stable_diffusion_2(
     ``guidance_rescale``: the model's default for ``generate()``.  ``snr_gamma``: Min-SNR-gamma loss weighting
     (``StableDiffusion``).  What any of them does to image quality with trained weights has not been measured here."""
     check_inference_scheduler(inference_scheduler)
+    inference_eta = _check_inference_eta(inference_eta, inference_scheduler)
     pt = _resolve_unet_config(model_name, unet_config, probe=True).prediction_type
     timestep_spacing = _check_zero_snr_options(zero_terminal_snr, pt, timestep_spacing, guidance_rescale, snr_gamma)
     if train_metrics is None:
@@ -196,6 +211,8 @@ def stable_diffusion_2(
     inference_noise_scheduler = make_inference_scheduler(inference_scheduler, prediction_type=unet_config.prediction_type,
                                                          rescale_betas_zero_snr=bool(zero_terminal_snr),
                                                          timestep_spacing=timestep_spacing)
+    if inference_eta:
+        inference_noise_scheduler.eta = inference_eta
 
     model = StableDiffusion(
         unet=unet,
@@ -244,10 +261,13 @@ def _pixel_unet(unet_config: Optional[UNetConfig], seed: int) -> UNetHIP:
 
 
 def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
-                             unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler: str = 'ddim'):
+                             unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler: str = 'ddim',
+                             inference_eta: float = 0.0):
     """Discrete-time (DDPM, 1000 steps) pixel diffusion; DDIM for inference (reference models.py:115-172), or with
-    ``inference_scheduler='dpm++2m'`` the second-order multistep solver (``DPMSolverMultistepScheduler``)."""
+    ``inference_scheduler='dpm++2m'`` the second-order multistep solver (``DPMSolverMultistepScheduler``), with
+    ``'dpm++2m-sde'`` its SDE form.  ``inference_eta``: the DDIM sampler's eta in [0, 1] (0: deterministic)."""
     check_inference_scheduler(inference_scheduler)
+    inference_eta = _check_inference_eta(inference_eta, inference_scheduler)
     if not torch.cuda.is_available():
         raise RuntimeError('discrete_pixel_diffusion: an MI355X is required (the U-Net has no CPU path)')
     unet = _pixel_unet(unet_config, seed)
@@ -257,6 +277,8 @@ def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch
     inference_scheduler = make_inference_scheduler(inference_scheduler, num_train_timesteps=1000, beta_start=0.00085,
                                                    beta_end=0.012, beta_schedule='scaled_linear', clip_sample=False,
                                                    steps_offset=1, prediction_type=prediction_type)
+    if inference_eta:
+        inference_scheduler.eta = inference_eta
     model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
                            prediction_type=prediction_type, train_metrics=[MeanSquaredError()],
                            val_metrics=[MeanSquaredError()])

@@ -18,10 +18,11 @@ from typing import List, Optional
 import torch
 
 from .. import ops
-from ..sampling import LatentSampler, resolve_sampler
+from ..sampling import LatentSampler, check_seed, image_seeds, philox_latents, resolve_sampler
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
-from .schedulers import check_inference_scheduler, resolve_inference_scheduler
-from .stable_diffusion import _HIPBackward, _check_prompt_given, _check_prompt_lenths, tqdm
+from .schedulers import check_eta, check_inference_scheduler, is_stochastic, resolve_inference_scheduler, with_eta
+from .stable_diffusion import (_HIPBackward, _check_prompt_given, _check_prompt_lenths, _philox_step_noise, _prompt_batch,
+                               tqdm)
 from .unet import UNetHIP
 
 _PREDICTION_TYPES = ('sample', 'epsilon', 'v_prediction')
@@ -184,7 +185,8 @@ class PixelDiffusion(ComposerModel):
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None, height: int = 64, width: int = 64,
                  num_inference_steps: Optional[int] = 50, guidance_scale: Optional[float] = 3.0,
                  num_images_per_prompt: Optional[int] = 1, seed: Optional[int] = None,
-                 progress_bar: Optional[bool] = True, sampler: Optional[str] = None, inference_scheduler=None):
+                 progress_bar: Optional[bool] = True, sampler: Optional[str] = None, inference_scheduler=None,
+                 eta: Optional[float] = None):
         """Reverse diffusion from noise with classifier-free guidance on the HIP U-Net forward (reference :137-241).
         Returns images in [0, 1], (batch * num_images_per_prompt, 3, h, w).
 
@@ -195,14 +197,30 @@ class PixelDiffusion(ComposerModel):
 
         ``inference_scheduler``: the solver of this call only: ``'ddim'``, ``'dpm++2m'`` (``DPMSolverMultistepScheduler``
         on the model's noise tables) or a scheduler object; default the model's own.  Discrete-time models only: a
-        continuous-time model raises ``ValueError`` for a name or a multistep scheduler."""
+        continuous-time model raises ``ValueError`` for a name or a multistep scheduler.
+
+        Stochastic discrete-time sampling: ``eta`` in [0, 1] is the DDIM sampler's eta for this call (default the
+        scheduler's own; ``ValueError`` with any other scheduler, the continuous-time one included) and
+        ``inference_scheduler='dpm++2m-sde'`` the SDE form of the two-step solver.  Their step noise comes from per-image
+        Philox streams (``ops.randn_philox``), the same values on every ``sampler=`` route.  ``seed`` may be a sequence of
+        one integer in [0, 2^64) per generated image: the initial noise then comes from the image's own stream too and
+        image i depends on nothing else in the batch.  With an int ``seed`` the initial noise stays on the torch generator
+        and image b's step noise has seed ``seed + b``; with None one base seed is drawn from the torch generator.  The
+        continuous-time Euler-Maruyama sampler keeps its ``torch.randn`` draws."""
         sampler = resolve_sampler(sampler)
         check_inference_scheduler(inference_scheduler)   # before `self` is read
+        if eta is not None:
+            check_eta(eta)
         scheduler = resolve_inference_scheduler(inference_scheduler, self.inference_scheduler, self.continuous_time)
+        scheduler = with_eta(scheduler, eta)
         _check_prompt_given(prompt, tokenized_prompts, prompt_embeds)
+        seed = check_seed(seed, _prompt_batch(prompt, tokenized_prompts, prompt_embeds) * num_images_per_prompt)
+        stochastic = not self.continuous_time and is_stochastic(scheduler)
         device = self.model.device_
         rng_generator = torch.Generator(device=device)
-        if seed:
+        if isinstance(seed, list):
+            rng_generator = rng_generator.manual_seed(seed[0] % 2**63)
+        elif seed:
             rng_generator = rng_generator.manual_seed(seed)
         self.model.check_spatial(int(height), int(width))   # pixels go in as they are: multiples of 2 ** (levels - 1)
         do_cfg = guidance_scale > 1.0
@@ -216,23 +234,29 @@ class PixelDiffusion(ComposerModel):
                                                    num_images_per_prompt)
             if sampler == 'torch':
                 text_embeddings = torch.cat([uncond, text_embeddings])
-        images = torch.randn((batch_size, self.model.config.in_channels, height, width), device=device,
-                             generator=rng_generator)
+        shape = (batch_size, self.model.config.in_channels, height, width)
+        if isinstance(seed, list):   # per-image seeds: the initial noise from the image's own stream
+            images = philox_latents(seed, shape, device)
+        else:
+            images = torch.randn(shape, device=device, generator=rng_generator)
+        seeds = image_seeds(seed, batch_size, stochastic, rng_generator)
         scheduler.set_timesteps(num_inference_steps)
         images = images * scheduler.init_noise_sigma
         if sampler != 'torch':
             images = LatentSampler(self.model, scheduler).sample(
                 images, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
-                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar)
+                guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar,
+                **(dict(seeds=seeds) if stochastic else {}))
         else:   # the reference's loop, the scheduler step in torch ops
-            for t in tqdm(scheduler.timesteps, disable=not progress_bar):
+            step_noise = _philox_step_noise(seeds, images.shape, device) if stochastic else (lambda i: {})
+            for i, t in enumerate(tqdm(scheduler.timesteps, disable=not progress_bar)):
                 model_input = torch.cat([images] * 2) if do_cfg else images
                 model_input = scheduler.scale_model_input(model_input, t)
                 model_output = self.model(model_input, t, encoder_hidden_states=text_embeddings).sample
                 if do_cfg:   # only technically correct for epsilon prediction (reference :226)
                     pred_uncond, pred_text = model_output.chunk(2)
                     model_output = pred_uncond + guidance_scale * (pred_text - pred_uncond)
-                images = scheduler.step(model_output, t, images, generator=rng_generator)['prev_sample']
+                images = scheduler.step(model_output, t, images, generator=rng_generator, **step_noise(i))['prev_sample']
         images = (images / 2 + 0.5).clamp(0, 1)
         return images.detach().float()
 

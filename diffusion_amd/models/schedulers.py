@@ -128,10 +128,14 @@ class _InferenceGrid:
 
 
 class DDIMScheduler(_InferenceGrid, DDPMScheduler):
-    """eta = 0 DDIM sampler, ``set_alpha_to_one=False``, ``steps_offset=1`` (SD-2 scheduler_config.json)."""
+    """DDIM sampler (Song et al., arXiv:2010.02502, eq. 12 and 16), ``set_alpha_to_one=False``, ``steps_offset=1`` (SD-2
+    scheduler_config.json).  ``eta`` = 0 (the default) is the deterministic sampler; ``eta`` in (0, 1] adds
+    sigma = eta sqrt((1 - abar_prev) / (1 - abar_t)) sqrt(1 - abar_t / abar_prev) of fresh noise per step and points the
+    rest of the variance, sqrt(1 - abar_prev - sigma^2), along the predicted noise; ``eta`` = 1 is DDPM ancestral sampling."""
 
-    def __init__(self, *a, steps_offset: int = 1, timestep_spacing: str = 'leading', **kw):
+    def __init__(self, *a, steps_offset: int = 1, timestep_spacing: str = 'leading', eta: float = 0.0, **kw):
         super().__init__(*a, **kw)
+        self.eta = check_eta(eta)
         self.steps_offset = steps_offset
         self.timestep_spacing = check_timestep_spacing(timestep_spacing)
         self.final_alpha_cumprod = self.alphas_cumprod[0]
@@ -158,13 +162,31 @@ class DDIMScheduler(_InferenceGrid, DDPMScheduler):
         if ac_t == 0.0 and self.prediction_type == 'epsilon':
             raise _zero_snr_epsilon_error(t)
         a, s, A, S = math.sqrt(ac_t), math.sqrt(1 - ac_t), math.sqrt(ac_prev), math.sqrt(1 - ac_prev)
+        if self.eta != 0.0:
+            # eta > 0: the same table with S' = sqrt(S^2 - sigma^2) where S stood, and cn = sigma for every prediction type
+            sigma = self._sigma(ac_t, ac_prev)
+            S = math.sqrt(max((1 - ac_prev) - sigma * sigma, 0.0))
+            if self.prediction_type == 'v_prediction':
+                return A * a + S * s, S * a - A * s, sigma
+            if self.prediction_type == 'sample':
+                return S / s, A - S * a / s, sigma
+            return A / a, S - A * s / a, sigma
         if self.prediction_type == 'v_prediction':
             return A * a + S * s, S * a - A * s, 0.0
         if self.prediction_type == 'sample':
             return S / s, A - S * a / s, 0.0
         return A / a, S - A * s / a, 0.0
 
-    def step(self, model_output, timestep, sample, generator=None, **kw):
+    def _sigma(self, ac_t: float, ac_prev: float) -> float:
+        """eta sqrt((1 - abar_prev) / (1 - abar_t)) sqrt(1 - abar_t / abar_prev) in float64; sigma^2 <= 1 - abar_prev because
+        the grid descends (abar_prev >= abar_t).  A step that goes nowhere (abar_prev == abar_t) has sigma 0."""
+        if self.eta == 0.0 or ac_t == 1.0:
+            return 0.0
+        return self.eta * math.sqrt((1 - ac_prev) / (1 - ac_t)) * math.sqrt(max(1 - ac_t / ac_prev, 0.0))
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, **kw):
+        if self.eta != 0.0:
+            return self._step_eta(model_output, timestep, sample, generator, variance_noise)
         t = int(timestep)
         prev_t = self._prev_timestep(t)
         if float(self.alphas_cumprod[t]) == 0.0 and self.prediction_type == 'epsilon':
@@ -188,6 +210,64 @@ class DDIMScheduler(_InferenceGrid, DDPMScheduler):
         return _Out(prev_sample=prev)
 
 
+    def _step_eta(self, model_output, timestep, sample, generator, variance_noise):
+        """``step`` for eta > 0, the coefficients in float64 from the fp32 table: prev = A x0 + sqrt(S^2 - sigma^2) eps +
+        sigma z, with z = ``variance_noise`` (diffusers' keyword), else a draw from ``generator``."""
+        t = int(timestep)
+        prev_t = self._prev_timestep(t)
+        ac_t = float(self.alphas_cumprod[t])
+        ac_prev = float(self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod)
+        if ac_t == 0.0 and self.prediction_type == 'epsilon':
+            raise _zero_snr_epsilon_error(t)
+        a, s, A = math.sqrt(ac_t), math.sqrt(1 - ac_t), math.sqrt(ac_prev)
+        sigma = self._sigma(ac_t, ac_prev)
+        Sp = math.sqrt(max((1 - ac_prev) - sigma * sigma, 0.0))
+        if self.prediction_type == 'v_prediction':
+            x0, eps = a * sample - s * model_output, a * model_output + s * sample
+        elif self.prediction_type == 'sample':
+            x0, eps = model_output, (sample - a * model_output) / s
+        else:
+            x0, eps = (sample - s * model_output) / a, model_output
+        if variance_noise is None:
+            variance_noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=sample.dtype)
+        prev = A * x0 + Sp * eps + sigma * variance_noise
+
+        class _Out(dict):
+            prev_sample = prev
+
+        return _Out(prev_sample=prev)
+
+
+def check_eta(eta) -> float:
+    """``eta=`` of ``DDIMScheduler``, the factories (``inference_eta``) and ``generate()``: a number in [0, 1], else
+    ``ValueError``.  Host only."""
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f'eta must be a number in [0, 1], got {eta!r}')
+    return float(eta)
+
+
+def with_eta(scheduler, eta):
+    """``generate(eta=...)``: ``scheduler`` itself for None or its own eta, else a shallow copy (same noise tables) with the
+    other eta for this call.  ``ValueError`` for eta outside [0, 1] and for a scheduler that is not a ``DDIMScheduler``."""
+    if eta is None:
+        return scheduler
+    eta = check_eta(eta)
+    if not isinstance(scheduler, DDIMScheduler):
+        raise ValueError(f'eta is the DDIM sampler\'s parameter: {type(scheduler).__name__} has none')
+    if scheduler.eta == eta:
+        return scheduler
+    import copy
+    sch = copy.copy(scheduler)
+    sch.eta = eta
+    return sch
+
+
+def is_stochastic(scheduler) -> bool:
+    """Whether a discrete-time scheduler adds noise in its steps (DDIM with eta > 0, the SDE solver): such a sample needs
+    per-image seeds."""
+    return getattr(scheduler, 'eta', 0.0) != 0.0 or getattr(scheduler, 'algorithm_type', None) == 'sde-dpmsolver++'
+
+
 class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
     """DPM-Solver++(2M) (Lu et al. 2022, arXiv:2211.01095, Algorithm 2): the second-order multistep solver of the diffusion ODE
     in the data-prediction parameterisation, deterministic, one model evaluation per step.  Same surface, timestep grid
@@ -204,14 +284,27 @@ class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
     The first step is first order; with ``lower_order_final`` and fewer than 15 steps the last one is too.
 
     ``step()`` is stateful (the previous x0 and lambda and a step index, reset by ``set_timesteps``).
-    ``step_coefficients_ms(i)`` is the same step as five floats, what ``ops.sampler_step_ms`` applies on the device."""
+    ``step_coefficients_ms(i)`` is the same step as five floats, what ``ops.sampler_step_ms`` applies on the device.
+
+    ``algorithm_type='sde-dpmsolver++'`` ("DPM++ 2M SDE", diffusers' midpoint update of the reverse SDE) is the same walk
+    with noise: with K = -alpha_t expm1(-2h)
+        x_t  = (sigma_t / sigma_s) e^{-h} x_s + K D + sigma_t sqrt(-expm1(-2h)) z,      z ~ N(0, I) fresh per step
+    and the same D, grid, order rules, zero-SNR rule and ``set_begin_index``.  ``step_coefficients_sde(i)`` is that step as
+    six floats (the row of ``ops.sampler_step_rng``); ``step()`` takes z as ``variance_noise=``, else draws it from
+    ``generator``.  ``step_coefficients_ms`` stays the ODE's five floats."""
 
     multistep = True
+    ALGORITHM_TYPES = ('dpmsolver++', 'sde-dpmsolver++')
+    default_algorithm_type = 'dpmsolver++'
 
     def __init__(self, *a, solver_order: int = 2, lower_order_final: bool = True, steps_offset: int = 1,
-                 timestep_spacing: str = 'leading', **kw):
+                 timestep_spacing: str = 'leading', algorithm_type: str = None, **kw):
         super().__init__(*a, **kw)
         self.timestep_spacing = check_timestep_spacing(timestep_spacing)
+        algorithm_type = self.default_algorithm_type if algorithm_type is None else algorithm_type
+        if algorithm_type not in self.ALGORITHM_TYPES:
+            raise ValueError(f'algorithm_type must be one of {self.ALGORITHM_TYPES}, got {algorithm_type!r}')
+        self.algorithm_type = algorithm_type
         if solver_order not in (1, 2):
             raise ValueError(f'solver_order must be 1 or 2, got {solver_order}')
         if self.prediction_type not in ('epsilon', 'v_prediction', 'sample'):
@@ -284,7 +377,25 @@ class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
         r = (l_s - self._alpha_sigma_lambda(int(self.timesteps[i - 1]))[2]) / h
         return ax, am, s_t / s_s, kd * (1.0 + 0.5 / r), -kd * (0.5 / r)
 
-    def step(self, model_output, timestep, sample, generator=None, **kw):
+    def step_coefficients_sde(self, i: int, first: bool = False):
+        """Step number ``i`` of the SDE solver as six Python floats (ax, am, kx, k0, k1, kn), computed in float64:
+        x0 = ax * sample + am * model_output, prev_sample = kx * sample + k0 * x0 + k1 * (the x0 of step i - 1) + kn * z.
+        kx = (sigma_t / sigma_s) e^{-h}; K = -alpha_t expm1(-2h) is k0 on a first-order step (k1 exactly 0.0), else
+        k0 = K (1 + 1/(2r)), k1 = -K / (2r); kn = sigma_t sqrt(-expm1(-2h)).  ``first`` as in ``step_coefficients_ms``."""
+        i = int(i)
+        t = int(self.timesteps[i])
+        a_s, s_s, l_s = self._alpha_sigma_lambda(t)
+        a_t, s_t, l_t = self._alpha_sigma_lambda(self._prev_timestep(t))
+        ax, am = self._data_prediction(a_s, s_s)
+        h = l_t - l_s
+        K = -a_t * math.expm1(-2.0 * h)
+        kx, kn = (s_t / s_s) * math.exp(-h), s_t * math.sqrt(-math.expm1(-2.0 * h))
+        if first or not self._second_order(i):
+            return ax, am, kx, K, 0.0, kn
+        r = (l_s - self._alpha_sigma_lambda(int(self.timesteps[i - 1]))[2]) / h
+        return ax, am, kx, K * (1.0 + 0.5 / r), -K * (0.5 / r), kn
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, **kw):
         t = int(timestep)
         a_s, s_s, l_s = self._alpha_sigma_lambda(t)
         a_t, s_t, l_t = self._alpha_sigma_lambda(self._prev_timestep(t))
@@ -295,7 +406,13 @@ class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
         if self._second_order(self._step_index) and self._prev_x0 is not None:
             r = (l_s - self._prev_lambda) / h
             d = (1.0 + 1.0 / (2.0 * r)) * x0 - (1.0 / (2.0 * r)) * self._prev_x0
-        prev = (s_t / s_s) * sample - (a_t * math.expm1(-h)) * d
+        if self.algorithm_type == 'sde-dpmsolver++':
+            if variance_noise is None:
+                variance_noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=sample.dtype)
+            prev = ((s_t / s_s) * math.exp(-h)) * sample - (a_t * math.expm1(-2.0 * h)) * d \
+                + (s_t * math.sqrt(-math.expm1(-2.0 * h))) * variance_noise
+        else:
+            prev = (s_t / s_s) * sample - (a_t * math.expm1(-h)) * d
         self._prev_x0, self._prev_lambda = x0, l_s
         self._step_index += 1
 
@@ -305,15 +422,29 @@ class DPMSolverMultistepScheduler(_InferenceGrid, DDPMScheduler):
         return _Out(prev_sample=prev)
 
 
+class DPMSolverSDEMultistepScheduler(DPMSolverMultistepScheduler):
+    """``DPMSolverMultistepScheduler`` whose default ``algorithm_type`` is ``'sde-dpmsolver++'``: what the name
+    ``'dpm++2m-sde'`` builds."""
+    default_algorithm_type = 'sde-dpmsolver++'
+
+
 INFERENCE_SCHEDULERS = {'ddim': DDIMScheduler, 'dpm++2m': DPMSolverMultistepScheduler}
+# the solvers that add noise in every step, a table of their own: every place that takes a name looks in both
+STOCHASTIC_INFERENCE_SCHEDULERS = {'dpm++2m-sde': DPMSolverSDEMultistepScheduler}
+
+
+def inference_scheduler_class(name: str):
+    """The class behind a scheduler name of either table; ``KeyError`` for an unknown one."""
+    return INFERENCE_SCHEDULERS[name] if name in INFERENCE_SCHEDULERS else STOCHASTIC_INFERENCE_SCHEDULERS[name]
 
 
 def check_inference_scheduler(scheduler, continuous_time: bool = False):
     """``inference_scheduler=`` of the factories and of ``generate()``: None, a name of ``INFERENCE_SCHEDULERS`` or a
     scheduler object.  Raises ``ValueError`` for an unknown name, and for a multistep scheduler on a continuous-time model
     (a discrete-time method), before anything touches the device."""
-    if isinstance(scheduler, str) and scheduler not in INFERENCE_SCHEDULERS:
-        raise ValueError(f'inference_scheduler must be one of {tuple(INFERENCE_SCHEDULERS)}, got {scheduler!r}')
+    if isinstance(scheduler, str) and scheduler not in INFERENCE_SCHEDULERS and scheduler not in STOCHASTIC_INFERENCE_SCHEDULERS:
+        raise ValueError(f'inference_scheduler must be one of {(*INFERENCE_SCHEDULERS, *STOCHASTIC_INFERENCE_SCHEDULERS)}, '
+                         f'got {scheduler!r}')
     if continuous_time and scheduler is not None and (isinstance(scheduler, str) or getattr(scheduler, 'multistep', False)):
         what = scheduler if isinstance(scheduler, str) else type(scheduler).__name__
         raise ValueError(f'inference_scheduler {what!r} is a discrete-time method: a continuous-time model samples with '
@@ -324,7 +455,7 @@ def make_inference_scheduler(name: str, like=None, **kw):
     """The inference scheduler called ``name``.  With ``like`` (a ``DDPMScheduler`` of any kind) it walks that scheduler's
     own noise tables with its ``prediction_type``, ``steps_offset`` and ``timestep_spacing``, read now."""
     check_inference_scheduler(name)
-    cls = INFERENCE_SCHEDULERS[name]
+    cls = inference_scheduler_class(name)
     if like is None:
         return cls(**kw)
     kw.setdefault('timestep_spacing', getattr(like, 'timestep_spacing', 'leading'))
@@ -343,7 +474,11 @@ def resolve_inference_scheduler(scheduler, own, continuous_time: bool = False):
     if scheduler is None:
         return own
     if isinstance(scheduler, str):
-        return own if type(own) is INFERENCE_SCHEDULERS[scheduler] else make_inference_scheduler(scheduler, like=own)
+        cls = inference_scheduler_class(scheduler)
+        # the two DPM names differ in the algorithm type, whichever class carries it
+        same = isinstance(own, cls) and getattr(own, 'algorithm_type', None) == getattr(cls, 'default_algorithm_type', None) \
+            if issubclass(cls, DPMSolverMultistepScheduler) else type(own) is cls
+        return own if same else make_inference_scheduler(scheduler, like=own)
     return scheduler
 
 

@@ -19,10 +19,12 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..sampling import LatentSampler, check_guidance_rescale, rescale_noise_cfg, resolve_sampler
+from ..sampling import (LatentSampler, check_guidance_rescale, check_seed, image_seeds, philox_latents, rescale_noise_cfg,
+                        resolve_sampler)
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
-from .schedulers import (check_inference_scheduler, check_snr_gamma, check_timestep_spacing, check_zero_snr_grid,
-                         min_snr_weights, resolve_inference_scheduler, with_timestep_spacing)
+from .schedulers import (check_eta, check_inference_scheduler, check_snr_gamma, check_timestep_spacing,
+                         check_zero_snr_grid, is_stochastic, min_snr_weights, resolve_inference_scheduler, with_eta,
+                         with_timestep_spacing)
 from .unet import UNetHIP
 from .vae import DiagonalGaussian
 
@@ -354,9 +356,21 @@ class StableDiffusion(ComposerModel):
                  width: Optional[int] = None, num_inference_steps: int = 50, guidance_scale: float = 3.0,
                  num_images_per_prompt: int = 1, seed: Optional[int] = None, progress_bar: bool = True,
                  guidance_rescale: Optional[float] = None, timestep_spacing: Optional[str] = None,
+                 eta: Optional[float] = None,
                  sampler: Optional[str] = None, inference_scheduler=None, init_image: Optional[torch.Tensor] = None,
                  strength: float = 0.8, mask: Optional[torch.Tensor] = None):
         """DDIM sampling with classifier-free guidance on the HIP U-Net forward (reference :260-382).
+
+        Stochastic sampling: ``eta`` in [0, 1] is the DDIM sampler's eta for this call (default the scheduler's own, 0 unless
+        the factory was given ``inference_eta``; 1 is DDPM ancestral sampling; ``ValueError`` with another solver), and
+        ``inference_scheduler='dpm++2m-sde'`` the SDE form of the two-step solver.  Their step noise comes from per-image
+        Philox streams (``ops.randn_philox``; drawn inside the step launch on the ``'hip'`` and ``'graph'`` routes, passed as
+        ``variance_noise`` on the ``'torch'`` route, the same values on all three).  ``seed`` may then be a sequence of one
+        integer in [0, 2^64) per generated image (the ``num_images_per_prompt`` copies included): the initial latents come
+        from the image's own stream too and image i depends on nothing else in the batch (up to the U-Net's batch-dependent
+        GEMM splits; the VAE posterior draw of ``init_image`` stays on the torch generator, seeded with the first entry).
+        With an int ``seed`` the initial latents stay on the torch generator and image b's step noise has seed ``seed + b``;
+        with None one base seed is drawn from the torch generator.
 
         ``sampler``: ``'hip'`` (``sampling.LatentSampler``: forward-only walk, context K/V projected once, one fused
         guidance + scheduler-step launch per step), ``'graph'`` (the same, one hipGraph replay per step) or ``'torch'``
@@ -391,10 +405,14 @@ class StableDiffusion(ComposerModel):
             _prompt_batch(prompt, tokenized_prompts, prompt_embeds) * num_images_per_prompt)
         scheduler, guidance_rescale = _resolve_sampling_options(
             inference_scheduler, self.inference_scheduler, guidance_rescale, self.guidance_rescale, timestep_spacing,
-            num_inference_steps)
+            num_inference_steps, eta)
+        seed = check_seed(seed, _prompt_batch(prompt, tokenized_prompts, prompt_embeds) * num_images_per_prompt)
+        stochastic = is_stochastic(scheduler)
         device = self.unet.device_
         rng = torch.Generator(device=device)
-        if seed:
+        if isinstance(seed, list):
+            rng = rng.manual_seed(seed[0] % 2**63)
+        elif seed:
             rng = rng.manual_seed(seed)
         vae_scale = 8
         height = height or self.unet.config.sample_size * vae_scale
@@ -417,8 +435,12 @@ class StableDiffusion(ComposerModel):
             z0 = self._encode_init_image(init_image, batch_size, rng)
             if mask is not None:
                 mask_px = mask.to(device, torch.float32).reshape(-1, height, width).expand(batch_size, -1, -1).contiguous()
-        latents = torch.randn((batch_size, self.unet.config.in_channels, height // vae_scale, width // vae_scale),
-                              device=device, generator=rng)
+        shape = (batch_size, self.unet.config.in_channels, height // vae_scale, width // vae_scale)
+        if isinstance(seed, list):   # per-image seeds: the initial noise from the image's own stream
+            latents = philox_latents(seed, shape, device)
+        else:
+            latents = torch.randn(shape, device=device, generator=rng)
+        seeds = image_seeds(seed, batch_size, stochastic, rng)
         scheduler.set_timesteps(num_inference_steps)
         latents = latents * scheduler.init_noise_sigma
         if sampler != 'torch':
@@ -426,9 +448,10 @@ class StableDiffusion(ComposerModel):
             latents = LatentSampler(self.unet, scheduler).sample(
                 latents, text_embeddings, uncond if do_cfg else None, num_inference_steps=num_inference_steps,
                 guidance_scale=guidance_scale, graph=sampler == 'graph', progress_bar=progress_bar,
-                guidance_rescale=guidance_rescale, **partial)
+                guidance_rescale=guidance_rescale, **partial, **(dict(seeds=seeds) if stochastic else {}))
         else:   # the reference's loop, the scheduler step in torch ops
             timesteps = scheduler.timesteps
+            step_noise = _philox_step_noise(seeds, latents.shape, device) if stochastic else (lambda i: {})
             if z0 is not None:   # the same method in torch ops: start from the noised image, run the tail of the schedule
                 noise = latents
                 latents = scheduler.add_noise(z0, noise, timesteps[start_index:start_index + 1])
@@ -444,7 +467,7 @@ class StableDiffusion(ComposerModel):
                 if do_cfg:
                     pu, pt = pred.chunk(2)
                     pred = rescale_noise_cfg(pu + guidance_scale * (pt - pu), pt, guidance_rescale)
-                latents = scheduler.step(pred, t, latents, generator=rng)['prev_sample']
+                latents = scheduler.step(pred, t, latents, generator=rng, **step_noise(i))['prev_sample']
                 if mask_px is not None:   # outside the mask: the known latent at the noise level of the next timestep
                     kn = scheduler.add_noise(z0, noise, timesteps[i + 1:i + 2]) if i + 1 < len(timesteps) else z0
                     latents = m * latents + (1 - m) * kn
@@ -497,15 +520,25 @@ def _check_loss_options(snr_gamma, loss_fn):
     return snr_gamma
 
 
+def _philox_step_noise(seeds, shape, device):
+    """The ``sampler='torch'`` route of a stochastic schedule: step i's noise as the ``variance_noise`` keyword of
+    ``scheduler.step``, the values the step kernel draws on the other routes (stream 0, draw number i)."""
+    seeds_dev = ops.philox_seeds(seeds, shape[0], device)
+    return lambda i: dict(variance_noise=ops.randn_philox(seeds_dev, i, 0, shape))
+
+
 def _resolve_sampling_options(inference_scheduler, own_scheduler, guidance_rescale, default_rescale, timestep_spacing,
-                              num_inference_steps):
-    """``generate(guidance_rescale=..., timestep_spacing=..., inference_scheduler=...)`` on the host: (the scheduler of this
-    call with its grid set, phi).  ``ValueError`` for phi outside [0, 1], an unknown spacing, and an epsilon-prediction
-    scheduler whose grid visits a timestep of zero SNR."""
+                              num_inference_steps, eta=None):
+    """``generate(guidance_rescale=..., timestep_spacing=..., inference_scheduler=..., eta=...)`` on the host: (the scheduler
+    of this call with its grid set, phi).  ``ValueError`` for phi or eta outside [0, 1], eta with a solver that has none, an
+    unknown spacing, and an epsilon-prediction scheduler whose grid visits a timestep of zero SNR."""
     phi = check_guidance_rescale(default_rescale if guidance_rescale is None else guidance_rescale)
+    if eta is not None:
+        check_eta(eta)
     if timestep_spacing is not None:
         check_timestep_spacing(timestep_spacing)
     scheduler = with_timestep_spacing(resolve_inference_scheduler(inference_scheduler, own_scheduler), timestep_spacing)
+    scheduler = with_eta(scheduler, eta)
     scheduler.set_timesteps(num_inference_steps)
     check_zero_snr_grid(scheduler)
     return scheduler, phi

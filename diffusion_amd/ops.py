@@ -767,20 +767,23 @@ def guidance_rescale(pred, coef, factor, *, phi, HW, C, g_index):
             or pred.shape[0] < 2 or pred.shape[0] % (2 * HW) or pred.data_ptr() % 16:
         raise ValueError(f'guidance_rescale: pred must be a contiguous fp32 [2 B * {HW}, 8] device tensor, 16-byte aligned')
     npix = pred.shape[0] // 2
-    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() not in (4, 8) \
-            or coef.data_ptr() % 16 or not 0 <= g_index < coef.numel():
-        raise ValueError('guidance_rescale: coef must be 4 or 8 contiguous fp32 on the device, 16-byte aligned, g_index inside')
+    if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() not in (4, 8, 12) \
+            or coef.data_ptr() % 16 or not 0 <= g_index < min(coef.numel(), 8):
+        raise ValueError('guidance_rescale: coef must be 4, 8 or 12 contiguous fp32 on the device, 16-byte aligned, g_index inside')
     _rescale_operands('guidance_rescale', factor, HW, npix)
     _lib.call('da_guidance_rescale', pred.data_ptr(), coef.data_ptr(), g_index, phi, factor.data_ptr(), npix, HW, C,
               _stream())
 
 
 def _sampler_step(ms, blend, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, *, noise=None, hist=None, known8=None,
-                  eps8=None, mask=None):
+                  eps8=None, mask=None, seeds=None):
     """The four step wrappers behind their signatures: the form is (``ms``: two-step, with ``hist`` and no ``noise``;
     ``blend``: masked, with ``known8`` / ``eps8`` / ``mask``), the checks are stated once and raise under the wrapper's name,
-    and the call goes to that form's symbol, its ``_rs`` twin when ``factor`` is given."""
-    fn = 'sampler_step' + ('_ms' if ms else '') + ('_blend' if blend else '')
+    and the call goes to that form's symbol, its ``_rs`` twin when ``factor`` is given.  With ``seeds`` (``sampler_step_rng``)
+    the row is the wider one, there is no ``noise`` operand and the call goes to ``da_sampler_step_rng`` with the form as a
+    mask."""
+    rng = seeds is not None
+    fn = 'sampler_step_rng' if rng else 'sampler_step' + ('_ms' if ms else '') + ('_blend' if blend else '')
     C, copies, cfg = int(C), int(copies), bool(cfg)
     if not 1 <= C <= 8 or copies not in (1, 2):
         raise ValueError(f'{fn}: C = {C} (1..8), copies = {copies} (1 or 2)')
@@ -798,7 +801,7 @@ def _sampler_step(ms, blend, pred, x, coef, x_out, xt_out, C, cfg, copies, facto
     # hist is written while the others are still being read
     if ms and hist.data_ptr() in [z.data_ptr() for z in (x, x_out, pred) + ((known8, eps8) if blend else ())]:
         raise ValueError(f'{fn}: hist must be a buffer of its own')
-    ncoef = 8 if ms or blend else 4
+    ncoef = (12 if ms else 8) if rng else 8 if ms or blend else 4
     if coef.dtype != F32 or not coef.is_cuda or not coef.is_contiguous() or coef.numel() != ncoef or coef.data_ptr() % 16:
         raise ValueError(f'{fn}: coef must be {ncoef} contiguous fp32 on the device, 16-byte aligned')
     HW_arg, HW = HW, npix
@@ -815,6 +818,18 @@ def _sampler_step(ms, blend, pred, x, coef, x_out, xt_out, C, cfg, copies, facto
             raise ValueError(f'{fn}: HW = {HW_arg} is not the noise draw\'s {HW} pixels per sample')
         HW = int(HW_arg)
     ptr = lambda z: z.data_ptr() if z is not None else None  # noqa: E731
+    if rng:
+        if HW_arg is None or int(HW_arg) < 1 or npix % int(HW_arg):
+            raise ValueError(f'{fn}: HW, the pixel count of one sample, must divide npix = {npix}; got {HW_arg}')
+        HW = int(HW_arg)
+        if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.uint64 or not seeds.is_cuda \
+                or not seeds.is_contiguous() or tuple(seeds.shape) != (npix // HW,) or seeds.data_ptr() % 8:
+            raise ValueError(f'{fn}: seeds must be a contiguous uint64 [{npix // HW}] device tensor')
+        _lib.call('da_sampler_step_rng', ptr(pred), ptr(x), ptr(hist if ms else None), ptr(coef),
+                  *((ptr(known8), ptr(eps8), ptr(mask)) if blend else (None, None, None)), ptr(factor), ptr(seeds),
+                  ptr(x_out), ptr(xt_out), npix, HW, C, (1 if ms else 0) | (2 if blend else 0) | (4 if factor is not None else 0),
+                  int(cfg), copies, _stream())
+        return
     _lib.call('da_' + fn + ('_rs' if factor is not None else ''), ptr(pred), ptr(x), ptr(hist if ms else noise), ptr(coef),
               *((ptr(known8), ptr(eps8), ptr(mask)) if blend else ()), *((ptr(factor),) if factor is not None else ()),
               ptr(x_out), ptr(xt_out), npix, HW, C, int(cfg), copies, _stream())
@@ -857,6 +872,67 @@ def sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x_out, xt_out
     ``hist`` receives the unblended data prediction.  ``coef`` = {ax, am, kx, k0, k1, guidance, bA, bS} on the device."""
     _sampler_step(True, True, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, hist=hist, known8=known8, eps8=eps8,
                   mask=mask)
+
+
+def sampler_step_rng(pred, x, coef, seeds, x_out, xt_out=None, *, HW, C, cfg, copies=1, hist=None, known8=None, eps8=None,
+                     mask=None, factor=None):
+    """The stochastic step (``da_sampler_step_rng``): any form of the step with its noise term drawn inside the kernel from
+    the per-image Philox streams of ``seeds`` (uint64 [npix / HW] on the device).  The form follows the operands: ``hist``
+    makes it two-step, ``known8`` / ``eps8`` / ``mask`` blended, ``factor`` rescaled.  ``coef`` on the device is
+    {cx, cm, cn, guidance, bA, bS, draw, 0} (first order) or {ax, am, kx, k0, k1, guidance, bA, bS, kn, draw, 0, 0}
+    (two-step), ``draw`` a uint32 bit pattern (``stochastic_rows`` of ``sampling`` writes it through an int32 view).  With
+    z = ``randn_philox(seeds, draw, 0, ...)`` the first-order forms give the bits of the deterministic wrapper fed z as
+    ``noise``; a zero noise coefficient draws nothing."""
+    ms, blend = hist is not None, mask is not None or known8 is not None or eps8 is not None
+    if blend and (mask is None or known8 is None or eps8 is None):
+        raise ValueError('sampler_step_rng: known8, eps8 and mask go together')
+    if seeds is None:
+        raise ValueError('sampler_step_rng: seeds is required')
+    _sampler_step(ms, blend, pred, x, coef, x_out, xt_out, C, cfg, copies, factor, HW, hist=hist, known8=known8, eps8=eps8,
+                  mask=mask, seeds=seeds)
+
+
+def philox_seeds(seeds, B=None, device=None):
+    """``seeds`` (a sequence or tensor of integers in [0, 2^64)) as the uint64 device tensor the Philox entries read; with
+    ``B`` its length is checked.  ``ValueError`` for anything else, raised before the upload."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype == torch.uint64 and (B is None or seeds.numel() == B) and seeds.dim() == 1:
+            return seeds.to(device).contiguous() if device is not None else seeds.contiguous()
+        seeds = seeds.tolist()
+    try:
+        vals = list(seeds)
+    except TypeError:
+        raise ValueError(f'seeds must be a sequence of integers, got {seeds!r}') from None
+    import numbers
+    if isinstance(seeds, (str, bytes)) or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals) \
+            or any(not 0 <= int(v) < 2**64 for v in vals) or (B is not None and len(vals) != B):
+        raise ValueError(f'seeds must be {B if B is not None else "a sequence of"} integers in [0, 2^64), got {seeds!r}')
+    # through int64 bit patterns: torch builds no uint64 tensor from Python ints above 2^63 - 1
+    t = torch.tensor([v - 2**64 if v >= 2**63 else v for v in map(int, vals)], dtype=torch.int64).view(torch.uint64)
+    return t.to(device) if device is not None else t
+
+
+def randn_philox(seeds, draw, stream, shape=None, *, out=None, kind=0):
+    """Per-image counter-based normals (``da_randn_philox``), the unfused form of the step kernels' draw: fp32 NCHW
+    [B, C, H, W] where image b's values depend on (seeds[b], draw, stream, pixel, channel) only.  ``seeds`` uint64 [B] on the
+    device; ``draw`` in [0, 2^32); ``stream`` 0 (step noise) or 1 (initial latents); ``kind`` 1 writes the raw Philox words
+    as bit patterns (C % 4 == 0).  Returns ``out`` (allocated with ``shape`` when not given)."""
+    if out is None:
+        if shape is None or len(shape) != 4:
+            raise ValueError('randn_philox: shape must be (B, C, H, W)')
+        out = torch.empty(tuple(int(v) for v in shape), device=seeds.device, dtype=F32)
+    if out.dim() != 4 or out.dtype != F32 or not out.is_cuda or not out.is_contiguous() or out.data_ptr() % 16 \
+            or out.numel() < 1 or not 1 <= out.shape[1] <= 8:
+        raise ValueError('randn_philox: out must be a contiguous fp32 [B, C, H, W] device tensor with C in 1..8')
+    B, C, H, W = out.shape
+    draw, stream, kind = int(draw), int(stream), int(kind)
+    if not 0 <= draw < 2**32 or stream not in (0, 1) or kind not in (0, 1) or (kind == 1 and C % 4) or H * W > 2**31 - 1:
+        raise ValueError(f'randn_philox: draw = {draw} (uint32), stream = {stream} (0 or 1), kind = {kind} (0, or 1 with C % 4 == 0)')
+    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.uint64 or not seeds.is_cuda or not seeds.is_contiguous() \
+            or tuple(seeds.shape) != (B,) or seeds.data_ptr() % 8:
+        raise ValueError(f'randn_philox: seeds must be a contiguous uint64 [{B}] device tensor')
+    _lib.call('da_randn_philox', seeds.data_ptr(), draw, stream, out.data_ptr(), B, C, H, W, kind, _stream())
+    return out
 
 
 def sampler_init(known, noise, coef, x, xt=None, *, known8=None, eps8=None, mask_px=None, mask=None, copies=1):

@@ -18,6 +18,10 @@ which replaces the state outside the mask by the known sample re-noised to the l
 With ``guidance_rescale`` = phi > 0 under guidance (Lin et al., arXiv:2305.08891) one more launch per step
 (``ops.guidance_rescale``: per sample phi std(pt) / std(m) + 1 - phi) precedes the step, whose ``_rs`` form multiplies the
 guided prediction by it.
+A stochastic discrete-time schedule (``DDIMScheduler`` with eta > 0, the SDE form of ``DPMSolverMultistepScheduler``) is
+the same loop with ONE other launch, ``ops.sampler_step_rng``: whatever the form (two-step, blended, rescaled), the step's
+noise term is drawn inside the kernel from per-image Philox streams (``sample(seeds=...)``), the draw number in the step's
+coefficient row, so it replays in the captured graph like any other step and an image's noise does not depend on its batch.
 Nothing in the loop reads the device back.  ``graph=True`` replays one captured step (walk + ``sampler_step``) per
 denoising step, as ``graph_step.GraphedMicrobatch`` does for a training microbatch; the host then issues two 16-byte-class
 copies (the step's timestep and coefficient rows) and a replay.
@@ -56,6 +60,37 @@ def check_guidance_rescale(phi) -> float:
     return float(phi)
 
 
+def check_seed(seed, batch_size: int):
+    """``generate(seed=...)`` on the host: None and an int pass through; a sequence (or tensor) is one seed per generated
+    image, the ``num_images_per_prompt`` copies included, and comes back as a list of ``batch_size`` ints in [0, 2^64).
+    ``ValueError`` otherwise, before anything touches the device."""
+    if seed is None or (isinstance(seed, int) and not isinstance(seed, bool)):
+        return seed
+    if isinstance(seed, (str, bytes, bool, float)):
+        raise ValueError(f'seed must be None, an int or a sequence of {batch_size} ints, got {seed!r}')
+    return [int(v) % 2**64 for v in ops.philox_seeds(seed, batch_size).view(torch.int64).tolist()]
+
+
+def image_seeds(seed, batch_size: int, stochastic: bool, generator) -> Optional[list]:
+    """The per-image Philox seeds of one ``generate()`` call, or None when nothing reads them.  ``seed`` is what
+    ``check_seed`` returned: a list is used as it is, whatever the sampler; with a stochastic sampler an
+    int gives image b the seed ``seed + b``, and None draws one base seed from ``generator`` (the call's torch generator,
+    after the initial latents: a deterministic call draws nothing more than it always did)."""
+    if isinstance(seed, list):
+        return list(seed)
+    if not stochastic:
+        return None
+    if seed is None:
+        seed = int(torch.randint(0, 2**62, (1,), generator=generator, device=generator.device).item())
+    return [(int(seed) + b) % 2**64 for b in range(batch_size)]
+
+
+def philox_latents(seeds, shape, device) -> torch.Tensor:
+    """Initial noise from the images' own streams: ``ops.randn_philox`` stream 1, draw 0, so image i of a call depends on
+    its seed and on nothing else in the batch."""
+    return ops.randn_philox(ops.philox_seeds(seeds, shape[0], device), 0, 1, shape)
+
+
 def rescale_noise_cfg(guided: torch.Tensor, cond: torch.Tensor, guidance_rescale: float) -> torch.Tensor:
     """diffusers' ``rescale_noise_cfg`` in torch ops, what the ``sampler='torch'`` loop applies: the guided prediction
     [B, C, H, W] scaled per sample back to the conditional prediction's standard deviation, blended by ``guidance_rescale``.
@@ -71,11 +106,14 @@ class GraphedSamplerStep:
     """One captured denoising step for one signature: forward-only walk + ``sampler_step`` over static buffers."""
 
     def __init__(self, unet, rows: int, B: int, HW, C: int, cfg: bool, t_dtype, ctx: torch.Tensor, kv: dict,
-                 multistep: bool = False, blend: bool = False, phi: float = 0.0):
+                 multistep: bool = False, blend: bool = False, phi: float = 0.0, rng: bool = False):
         dev = unet.device_
         H, W = HW
         self.unet, self.rows, self.HW, self.C, self.cfg, self.multistep = unet, rows, (H, W), C, cfg, multistep
         self.blend = blend
+        # a stochastic schedule: the captured launch is sampler_step_rng, which reads the per-image seeds from a static
+        # buffer (filled by load) and the step's draw number from the coefficient row like everything else
+        self.seeds = torch.zeros(B, device=dev, dtype=torch.int64).view(torch.uint64) if rng else None
         # guidance rescale: phi is a launch argument of the captured statistics pass, so it is part of the cache key
         self.phi = phi
         self.factor = torch.ones(B, device=dev, dtype=torch.float32) if phi > 0.0 else None
@@ -83,7 +121,7 @@ class GraphedSamplerStep:
         self.x = torch.zeros(npix, 8, device=dev, dtype=torch.float32)
         self.xt = torch.zeros(rows * H * W, 8, device=dev, dtype=torch.bfloat16)
         self.t = torch.zeros(rows, device=dev, dtype=t_dtype)
-        self.coef = torch.zeros(8 if multistep or blend else 4, device=dev, dtype=torch.float32)
+        self.coef = torch.zeros(coef_row_width(multistep, blend, rng), device=dev, dtype=torch.float32)
         # a masked sample: the known sample, its noise draw and the mask, written by sampler_init before the first replay
         self.known8 = torch.zeros(npix, 8, device=dev, dtype=torch.float32) if blend else None
         self.eps8 = torch.zeros(npix, 8, device=dev, dtype=torch.float32) if blend else None
@@ -108,13 +146,15 @@ class GraphedSamplerStep:
     def _body(self):
         pred = self.unet.forward_features(self.xt, self.t, self.ctx, self.rows, self.HW, kv=self.kv, record=False)
         rs = _rescale_pass(pred, self.coef, self.factor, self.phi, self.HW[0] * self.HW[1], self.C, self.multistep)
-        _step_launch(pred, self.x, self.hist, self.known8, self.eps8, self.mask, self.xt, self.coef, None, C=self.C,
-                     cfg=self.cfg, copies=2 if self.cfg else 1, **rs)
+        _step_launch(pred, self.x, self.hist, self.known8, self.eps8, self.mask, self.xt, self.coef, None, self.seeds,
+                     self.HW[0] * self.HW[1], C=self.C, cfg=self.cfg, copies=2 if self.cfg else 1, **rs)
 
-    def load(self, ctx, kv):
+    def load(self, ctx, kv, seeds=None):
         self.ctx.copy_(ctx, non_blocking=True)
         for k, v in kv.items():
             self.kv[k].copy_(v, non_blocking=True)
+        if self.seeds is not None:   # as int64 bit patterns: the copy needs no uint64 kernel
+            self.seeds.view(torch.int64).copy_(seeds.view(torch.int64), non_blocking=True)
 
     def step(self, t_row, coef_row):
         self.t.copy_(t_row, non_blocking=True)
@@ -131,11 +171,33 @@ def _rescale_pass(pred, coef, factor, phi, HW, C, multistep):
     return dict(factor=factor, HW=HW)
 
 
-def _step_launch(pred, x, hist, known8, eps8, mask, xt, coef, noise, **kw):
+def coef_row_width(multistep: bool, blend: bool, rng: bool) -> int:
+    """Floats in one step's coefficient row: 4, 8 with a history or a blend; a stochastic (``rng``) row is one vector wider
+    than the widest deterministic one of its order (8 first order, 12 two-step)."""
+    if rng:
+        return 12 if multistep else 8
+    return 8 if multistep or blend else 4
+
+
+def stochastic_rows(rows, draw_slot: int, draws) -> torch.Tensor:
+    """The fp32 host table of a stochastic schedule's rows: the floats through float64 -> float32 like every table, then the
+    draw numbers (uint32 values) into column ``draw_slot`` as BIT PATTERNS through an int32 view, never through a float
+    conversion (a float holds no integer above 2^24 exactly and the kernel bit-casts the slot back)."""
+    tab = torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+    bits = torch.tensor([d - 2**32 if d >= 2**31 else d for d in (int(d) & 0xffffffff for d in draws)], dtype=torch.int32)
+    tab.view(torch.int32)[:, draw_slot] = bits
+    return tab
+
+
+def _step_launch(pred, x, hist, known8, eps8, mask, xt, coef, noise, seeds=None, hw=None, **kw):
     """The step launch for this sampler state, in place: the two-step form when there is a history buffer, the blended
     form when there is a mask; ``noise`` is the first-order forms' draw (None without one), ``kw`` the keywords of the step
-    wrappers (``C``, ``cfg``, ``copies`` and what ``_rescale_pass`` returned)."""
-    if mask is not None and hist is not None:
+    wrappers (``C``, ``cfg``, ``copies`` and what ``_rescale_pass`` returned).  With ``seeds`` (a stochastic discrete-time
+    schedule) it is the one launch that draws in the kernel, whatever the form; ``hw`` is then the sample's pixel count."""
+    if seeds is not None:
+        kw.setdefault('HW', hw)
+        ops.sampler_step_rng(pred, x, coef, seeds, x, xt, hist=hist, known8=known8, eps8=eps8, mask=mask, **kw)
+    elif mask is not None and hist is not None:
         ops.sampler_step_ms_blend(pred, x, hist, coef, known8, eps8, mask, x, xt, **kw)
     elif mask is not None:
         ops.sampler_step_blend(pred, x, coef, known8, eps8, mask, x, xt, noise, **kw)
@@ -173,7 +235,7 @@ class LatentSampler:
                num_inference_steps: int, guidance_scale: float, graph: bool = False,
                progress_bar: bool = False, known: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                start_index: int = 0, mask_px: Optional[torch.Tensor] = None,
-               guidance_rescale: float = 0.0) -> torch.Tensor:
+               guidance_rescale: float = 0.0, seeds=None) -> torch.Tensor:
         """latents: the initial noise [B, C, H, W] (already scaled by ``init_noise_sigma``); cond / uncond: [B, L, D] text
         states.  Classifier-free guidance runs iff ``guidance_scale > 1.0`` (``uncond`` is then required).  Returns the
         denoised [B, C, H, W] fp32 (latent models: before the 1 / 0.18215 rescale).
@@ -184,8 +246,12 @@ class LatentSampler:
         needs ``known``): fp32 [B, f H, f W] in [0, 1] at f x f pixels per state pixel (f a power of two in 1..16; 8 for the
         latent models), 1 = repaint, 0 = keep; its f x f box mean weighs every step's blend with the re-noised known
         sample.  ``guidance_rescale`` (phi in [0, 1]): under guidance and with phi > 0 every step scales the guided
-        prediction per sample by phi std(pt) / std(m) + 1 - phi; otherwise the launches are the ones without it.  Every
-        check of these raises ``ValueError`` before anything is launched."""
+        prediction per sample by phi std(pt) / std(m) + 1 - phi; otherwise the launches are the ones without it.
+        ``seeds``: B integers in [0, 2^64) (a sequence or tensor), required by a stochastic discrete-time schedule (DDIM with
+        eta > 0, the SDE solver) and not read otherwise: step ``i`` adds its noise coefficient times image b's Philox draw
+        number ``i`` of stream 0 (``ops.randn_philox(seeds, i, 0)``), drawn inside the step launch, on the eager and the
+        graph route alike, with ``known`` / ``mask_px`` and with ``guidance_rescale``.  Every check of these raises
+        ``ValueError`` before anything is launched."""
         unet, sch = self.unet, self.scheduler
         phi = check_guidance_rescale(guidance_rescale)
         if known is None:
@@ -228,6 +294,14 @@ class LatentSampler:
             if not 0 <= int(start_index) < n:
                 raise ValueError(f'start_index must lie in [0, {n}), got {start_index}')
         start = int(start_index)
+        # a stochastic discrete-time schedule draws in the step kernel from per-image streams; the continuous-time
+        # Euler-Maruyama path keeps its torch.randn draw below
+        from .models.schedulers import is_stochastic   # here: models imports this module
+        rng = not continuous and is_stochastic(sch)
+        if rng:
+            if seeds is None:
+                raise ValueError(f'{type(sch).__name__} adds noise in its steps: sample() needs seeds, one integer per image')
+            seeds = ops.philox_seeds(seeds, B)
         dev = unet.device_
         # per-call device tables, one upload each: the timestep of every step for every row, {cx, cm, cn, guidance}
         # (a two-step scheduler: {ax, am, kx, k0, k1, guidance, 0, 0}, and no noise term)
@@ -239,26 +313,41 @@ class LatentSampler:
         if multistep:
             # the first executed step of a schedule entered late has no history: first order
             first = [known is not None and i == start for i in range(n)]
-            coef_rows = [list(sch.step_coefficients_ms(i, first=True) if first[i] else sch.step_coefficients_ms(i))
-                         + [float(guidance_scale), *renoise[i]] for i in range(n)]
             stochastic = False
+            if rng:   # {ax, am, kx, k0, k1, guidance, bA, bS, kn, draw, 0, 0}: step i uses draw number i
+                sde = [sch.step_coefficients_sde(i, first=first[i]) for i in range(n)]
+                coef_rows = [list(r[:5]) + [float(guidance_scale), *renoise[i], r[5], 0.0, 0.0, 0.0] for i, r in enumerate(sde)]
+            else:
+                coef_rows = [list(sch.step_coefficients_ms(i, first=True) if first[i] else sch.step_coefficients_ms(i))
+                             + [float(guidance_scale), *renoise[i]] for i in range(n)]
         else:
             coefs = [sch.step_coefficients(t) for t in ts]
-            coef_rows = [[cx, cm, cn, float(guidance_scale)] + ([*renoise[i], 0.0, 0.0] if blend else [])
-                         for i, (cx, cm, cn) in enumerate(coefs)]
-            stochastic = any(cn != 0.0 for _, _, cn in coefs)
-        coef_tab = torch.tensor(coef_rows, dtype=torch.float64).to(torch.float32).to(dev)
+            if rng:   # {cx, cm, cn, guidance, bA, bS, draw, 0}
+                coef_rows = [[cx, cm, cn, float(guidance_scale), *renoise[i], 0.0, 0.0] for i, (cx, cm, cn) in enumerate(coefs)]
+                stochastic = False
+            else:
+                coef_rows = [[cx, cm, cn, float(guidance_scale)] + ([*renoise[i], 0.0, 0.0] if blend else [])
+                             for i, (cx, cm, cn) in enumerate(coefs)]
+                stochastic = any(cn != 0.0 for _, _, cn in coefs)
+        if rng:
+            coef_tab = stochastic_rows(coef_rows, 9 if multistep else 6, range(n)).to(dev)
+            seeds = seeds.to(dev)
+        else:
+            seeds = None   # a deterministic schedule reads none: the launches are the ones it always had
+            coef_tab = torch.tensor(coef_rows, dtype=torch.float64).to(torch.float32).to(dev)
         # the context: cast once, projected once
         enc = torch.cat([uncond.to(dev), cond.to(dev)]) if cfg else cond.to(dev)
         ctx = unet.prepare_ctx(enc)
         kv = unet.project_context(ctx)
         copies = 2 if cfg else 1
         g = None
-        if graph and not stochastic and ops.PROFILE is None:   # the SDE needs a fresh draw per step: eager
+        # the continuous-time SDE needs a fresh torch draw per step: eager.  A discrete-time stochastic schedule draws in
+        # the kernel, its draw number in the row: it replays like any other
+        if graph and not stochastic and ops.PROFILE is None:
             key = (rows, H, W, C, cfg, t_dtype, ctx.shape[0] // rows, ctx.shape[1]) + (('multistep',) if multistep else ()) \
-                + (('blend',) if blend else ()) + (('rescale', phi) if phi > 0.0 else ())
-            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep, blend, phi)
-            g.load(ctx, kv)
+                + (('blend',) if blend else ()) + (('rescale', phi) if phi > 0.0 else ()) + (('rng',) if rng else ())
+            g = self._graph_for(key, rows, B, (H, W), C, cfg, t_dtype, ctx, kv, multistep, blend, phi, rng)
+            g.load(ctx, kv, seeds)
             x, xt, hist = g.x, g.xt, g.hist
             known8, eps8, mask = g.known8, g.eps8, g.mask
             x.zero_()
@@ -291,6 +380,6 @@ class LatentSampler:
             # the Euler-Maruyama draw: global generator, after the U-Net call, the shape step() draws (randn_like(sample));
             # a masked sample is discrete time: no draw
             noise = torch.randn((B, C, H, W), device=dev) if stochastic and not blend else None
-            _step_launch(pred, x, hist, known8, eps8, mask, xt if i + 1 < n else None, coef_tab[i], noise, C=C, cfg=cfg,
-                         copies=copies, **rs)
+            _step_launch(pred, x, hist, known8, eps8, mask, xt if i + 1 < n else None, coef_tab[i], noise, seeds, H * W, C=C,
+                         cfg=cfg, copies=copies, **rs)
         return x.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2).contiguous()

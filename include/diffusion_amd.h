@@ -334,6 +334,39 @@ int da_sampler_step_blend_rs(const float* pred, const float* x, const float* noi
 int da_sampler_step_ms_blend_rs(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
                                 const float* eps8, const float* mask, const float* factor, float* x_out, void* xt_out,
                                 long npix, int HW, int C, int cfg, int copies, da_stream_t stream);
+/* The counter-based normal generator of the stochastic samplers, unfused: Philox4x32-10 (Salmon et al., SC'11; multipliers
+ * 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds) and Box-Muller.  For image b, pixel
+ * pix = h W + w and channel block k = c / 4:
+ *   key     = (seeds[b] & 0xffffffff, seeds[b] >> 32)
+ *   counter = (pix, draw, stream, k)                 stream 0: step noise, 1: initial latents
+ *   (r0, r1) -> channels 4k, 4k + 1 and (r2, r3) -> channels 4k + 2, 4k + 3: for a pair (ra, rb)
+ *   u = ((ra >> 9) + 0.5) 2^-23 (exact, in (0, 1)),  theta = 2 pi (rb >> 8) 2^-24,
+ *   z_even = sqrt(-2 ln u) cos theta,  z_odd = sqrt(-2 ln u) sin theta              |z| <= 5.77; channels >= C are dropped
+ * in fp32 with the accurate logf / sincospif / sqrtf.  So a value depends on (seed of its image, draw, stream, pixel, channel)
+ * and on nothing else: not on B, not on the image's place in the batch.
+ *   seeds  DEVICE uint64 [B], 8-byte aligned;  out fp32 NCHW [B][C][H][W], 16-byte aligned;
+ *   kind 0 writes the normals, kind 1 the raw words r0..r3 as bit patterns in their place (needs C % 4 == 0).
+ * da_sampler_step_rng draws the same values inside the step.  DA_ERR_SHAPE for B, H or W <= 0, H W > 2^31 - 1, C outside
+ * 1..8, stream outside {0, 1}, kind outside {0, 1}, kind 1 with C % 4, a NULL or misaligned pointer. */
+int da_randn_philox(const unsigned long long* seeds, unsigned draw, unsigned stream, float* out, int B, int C, int H, int W,
+                    int kind, da_stream_t hip_stream);
+/* The stochastic step: any of the eight forms above with the noise term drawn inside the kernel.  `form` is a mask:
+ * 1 two-step (hist), 2 blended (known8 / eps8 / mask), 4 rescaled (factor); the operands of a form that is not selected are
+ * not read and may be NULL.  seeds: DEVICE uint64 [npix / HW], 8-byte aligned, required; HW is the pixel count of one
+ * sample.  The row is wider, and the draw number travels in it as a uint32 BIT PATTERN in a float slot (write it through an
+ * integer view, never through a float conversion):
+ *   first order   eight floats  {cx, cm, cn, guidance, bA, bS, draw, 0}             (bA, bS read by the blended form only)
+ *   two-step      twelve floats {ax, am, kx, k0, k1, guidance, bA, bS, kn, draw, 0, 0}
+ * With z = da_randn_philox(seeds, draw, stream 0) at the pixel, the order is guidance, rescale, the update, then
+ *   first order:  v = cx x + cm m + cn z            the bits da_sampler_step* gives when fed z as its noise operand
+ *   two-step:     v = (kx x + k0 x0 (+ k1 hist)) + kn z            product and sum each rounded (no FMA)
+ * then the blend; hist keeps the unblended, noise-free data prediction.  The kernel draws iff the noise coefficient (cn, kn)
+ * is not 0 - one test for the whole launch - and a row with a zero coefficient gives the deterministic entry's bits.
+ * DA_ERR_SHAPE as for the entry of the same form, and for form outside 0..7, a NULL or misaligned seeds, HW > 2^31 - 1. */
+int da_sampler_step_rng(const float* pred, const float* x, float* hist, const float* coef, const float* known8,
+                        const float* eps8, const float* mask, const float* factor, const unsigned long long* seeds,
+                        float* x_out, void* xt_out, long npix, int HW, int C, int form, int cfg, int copies,
+                        da_stream_t stream);
 /* The start of a sample that begins from an image (image-to-image, inpainting), one launch:
  *   known   fp32 NCHW [B][C][H][W], the clean sample (latent models: already scaled); noise the same shape;
  *   mask_px NULL, or fp32 [B][f H][f W], the mask at f x f pixels per state pixel, f a power of two in 1..16;
