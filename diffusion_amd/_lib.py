@@ -94,6 +94,8 @@ SIGNATURES = {
     'da_cast_f32_bf16': [_fp, _vp, _l, _vp],
     'da_transpose_weight': [_vp, _vp, _i, _i, _i, _vp],
     'da_transpose_weights_batched': [_vp, _vp, _vp, _i, _i, _vp],
+    'da_lora_merge': [_fp, _fp, _vp, _i, _i, _vp, _fp, _vp],
+    'da_lora_project': [_fp, _fp, _vp, _i, _i, _i, _fp, _vp],
 }
 _RESTYPES = {'da_norm_scratch_floats': C.c_long, 'da_segment_sumsq_scratch_floats': C.c_long}
 

@@ -88,11 +88,13 @@ class GraphStepCache:
     def usable(self, batch) -> bool:
         """Only latent-space models with precomputed latents are captured: a model without them (PixelDiffusion encodes
         its captions every step and has no latent keys) runs eagerly.  So does a model with ``snr_gamma`` set: its
-        timestep-weighted loss launch is not part of the captured microbatch, and declining keeps the weighting."""
+        timestep-weighted loss launch is not part of the captured microbatch, and declining keeps the weighting.  So does a
+        U-Net that carries LoRA adapters: a graph captured before they were attached would replay the skipped weight
+        gradients."""
         m = self.model
         return (ops.PROFILE is None and getattr(m, 'precomputed_latents', False) and m.image_latents_key in batch
                 and m.text_latents_key in batch and m.loss_fn is torch.nn.functional.mse_loss
-                and getattr(m, 'snr_gamma', None) is None)
+                and getattr(m, 'snr_gamma', None) is None and getattr(getattr(m, 'unet', None), 'lora', None) is None)
 
     def step(self, batch, weight: float):
         """Forward + loss + backward of one microbatch by graph replay.  Returns (outputs, loss) like the eager pair

@@ -130,8 +130,13 @@ def stable_diffusion_2(
     timestep_spacing: Optional[str] = None,
     guidance_rescale: float = 0.0,
     inference_eta: float = 0.0,
+    lora_path: Optional[str] = None,
+    lora_scale: float = 1.0,
 ):
-    """``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's),
+    """``lora_path``: a safetensors LoRA file (diffusion_amd/lora.py) attached to the U-Net at ``lora_scale`` times its own
+    alpha / r; sampling and evaluation then run with the adapted weights (``model.unload_lora()`` restores the base).
+
+    ``inference_scheduler``: the solver ``generate()`` and ``eval_forward`` sample with, ``'ddim'`` (the reference's),
     ``'dpm++2m'`` (``DPMSolverMultistepScheduler``) or ``'dpm++2m-sde'`` (its SDE form: noise in every step).
     ``inference_eta``: the DDIM sampler's eta in [0, 1] (``ValueError`` above 0 with another solver); above 0 the sampler
     is stochastic, 1 is DDPM ancestral sampling.  ``eval_forward``, the image metrics and the image logger follow both, with
@@ -235,6 +240,8 @@ def stable_diffusion_2(
     model.vae_hip = vae_hip if build_encoders else None
     model.vae_dec_hip = vae_dec_hip if build_encoders else None
     model.text_hip = text_hip if build_encoders else None
+    if lora_path:
+        model.load_lora(lora_path, lora_scale)
     return model
 
 

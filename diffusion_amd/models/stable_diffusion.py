@@ -297,6 +297,18 @@ class StableDiffusion(ComposerModel):
         self._run_backward(None)
 
     # ------------------------------------------------------------------------------------------
+    # LoRA adapters (diffusion_amd/lora.py): the U-Net's bf16 weight shadows carry them, so generate(), eval_forward, the
+    # metrics and every sampler route follow without knowing
+    def load_lora(self, path: str, scale: float = 1.0):
+        return self.unet.load_lora(path, scale)
+
+    def unload_lora(self):
+        self.unet.remove_lora()
+
+    def set_lora_scale(self, x: float):
+        self.unet.set_lora_scale(x)
+
+    # ------------------------------------------------------------------------------------------
     def eval_forward(self, batch, outputs=None):
         if outputs is not None:
             return outputs

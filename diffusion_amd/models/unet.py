@@ -365,6 +365,8 @@ class UNetHIP(nn.Module):
         self._tape = None
         self._kv, self._record = None, True   # the forward-only walk of sampling sets these for its duration
         self._ctx = self._tproj = None
+        self.lora = None           # diffusion_amd.lora.LoRAAdapters while adapters are attached (add_lora / load_lora)
+        self._lora_gw = frozenset()   # data_ptr of the gradient views of the storages that carry one
         if init:
             self.reset_parameters(seed)
 
@@ -453,7 +455,71 @@ class UNetHIP(nn.Module):
         """master fp32 -> bf16 compute shadow and the transposed (dgrad) shadow.  Call after any direct edit of
         the parameters; the fused optimizer step does it itself."""
         ops.cast_f32_bf16(self.master, self.shadow)
+        if self.lora is not None:   # adapted row ranges: bf16(master + s B A) instead of bf16(master)
+            ops.lora_merge(self.master, self.lora, self.shadow)
         self.refresh_transposed()
+
+    # ------------------------------------------------------------------------------------------
+    # LoRA adapters (diffusion_amd/lora.py): the base stays frozen in the master, the shadows carry master + s B A
+    # ------------------------------------------------------------------------------------------
+    def _attach_lora(self, adapters):
+        if self.lora is not None:
+            raise RuntimeError('the U-Net already carries adapters (one at a time): remove_lora() or fuse_lora() first')
+        self.lora = adapters.to(self.device_)
+        self._lora_gw = frozenset(self._mats[s].gw.data_ptr() for s in adapters.storages)
+        return adapters
+
+    def add_lora(self, rank: int, alpha: Optional[float] = None, target_modules=None, seed: int = 17):
+        """Attach fresh adapters (A ~ kaiming-uniform, B = 0: the shadows keep their bits until B moves).  While they are
+        attached the master is frozen: weight gradients of matrices without an adapter are skipped, FusedAdamW.attach_lora()
+        trains the adapter buffers, and sync_shadows() ends with the merge."""
+        from ..lora import LoRAAdapters
+        self._attach_lora(LoRAAdapters(self.fp, rank, alpha, target_modules, seed))
+        self.sync_shadows()
+        return self.lora
+
+    def remove_lora(self):
+        """Drop the adapters: the shadows are bf16(master) again, bit for bit."""
+        self.lora, self._lora_gw = None, frozenset()
+        self.sync_shadows()
+
+    def set_lora_scale(self, x: float):
+        """Re-merge with s * x (sampling at another strength; 0 gives the base's shadows bit for bit)."""
+        if self.lora is None:
+            raise RuntimeError('set_lora_scale: no adapters attached')
+        self.lora.scale_mult = float(x)
+        self.lora.upload_table()
+        self.sync_shadows()
+
+    def fuse_lora(self):
+        """master <- master + s B A (the fp32 value the merge rounds, so the fused master casts to the same shadow bits),
+        then drop the adapters."""
+        if self.lora is None:
+            raise RuntimeError('fuse_lora: no adapters attached')
+        ops.lora_merge(self.master, self.lora, self.shadow, vout=self.master)
+        self.remove_lora()
+
+    def save_lora(self, path: str):
+        if self.lora is None:
+            raise RuntimeError('save_lora: no adapters attached')
+        from ..lora import save_file
+        save_file(self.lora, path)
+
+    def load_lora(self, path: str, scale: float = 1.0):
+        """Attach the adapters of a safetensors file (PEFT / diffusers key names; rank, alpha and targets from its metadata)
+        and merge them at ``scale`` times their own alpha / r."""
+        from ..lora import LoRAAdapters, read_file
+        sd, rank, alpha, targets = read_file(path)
+        ad = self._attach_lora(LoRAAdapters(self.fp, rank, alpha, targets))
+        try:
+            ad.load_state_dict(sd)
+        except Exception:
+            self.lora, self._lora_gw = None, frozenset()
+            raise
+        ad.scale_mult = float(scale)
+        ad.upload_table()
+        self.sync_shadows()
+        return ad
 
     def refresh_transposed(self):
         """shadow [N][T][C] -> dgrad shadow [C][T-1-t][N] for every weight matrix, in one launch."""
@@ -564,6 +630,8 @@ class UNetHIP(nn.Module):
         ``wgrad_stream`` set it is issued on a second stream behind an event on its operands: the 256-workgroup wgrad grids
         then share the chip with whatever the main stream runs next, and the HBM-bound links of the chain (norm / GEGLU /
         short-K dgrad kernels, which cannot use the matrix pipes) stop costing wall time of their own."""
+        if self.lora is not None and gw.data_ptr() not in self._lora_gw:
+            return   # frozen base: only matrices that carry an adapter need dW (lora_project turns it into dA, dB)
         ws = self.wgrad_stream
         if ws is None:
             d = self._wgrad_defer
@@ -775,7 +843,8 @@ class UNetHIP(nn.Module):
         dg = self._lin_bwd(g, dh0, p + '.proj_in')
         if self._wgrad_defer is not None:   # every gradient of the block is final when it returns (_grad_ready_cb contract)
             items, self._wgrad_defer = self._wgrad_defer[1], None
-            ops.gemm_tn_wgrad_group(items, M)
+            if items:   # empty only when adapters are attached and none of them sits on this block's linears
+                ops.gemm_tn_wgrad_group(items, M)
             del items
         return self._gn_bwd(x, dg, dout, p + '.norm', gst, B, HW, 0)
 

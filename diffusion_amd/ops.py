@@ -1111,3 +1111,33 @@ def transpose_weights_batched(src_base, dst_base, desc, ntensors, total_blocks):
         raise ValueError('transpose_weights_batched: bad args')
     _lib.call('da_transpose_weights_batched', src_base.data_ptr(), dst_base.data_ptr(), desc.data_ptr(), int(ntensors),
               int(total_blocks), _stream())
+
+
+def _lora_check(name, adapters, *bufs):
+    if adapters.table is None or not adapters.table.is_cuda:
+        raise ValueError(f'{name}: the adapter layout is not on the device (LoRAAdapters.to(device))')
+    for z, n, what in bufs:
+        if z.dtype != F32 or not z.is_cuda or not z.is_contiguous() or z.numel() < n:
+            raise ValueError(f'{name}: {what} must be a contiguous fp32 device buffer of >= {n} elements')
+
+
+def lora_merge(master, adapters, shadow, vout=None):
+    """shadow = bf16(master + s B A) on the row ranges of ``adapters`` (diffusion_amd.lora.LoRAAdapters on the device), one
+    launch; ``vout`` (fp32, may be ``master``) receives the unrounded value.  Follow it with refresh_transposed()."""
+    _lora_check('lora_merge', adapters, (master, adapters.master_extent, 'master'), (adapters.params, adapters.total, 'params'))
+    if shadow.dtype != BF16 or not shadow.is_cuda or not shadow.is_contiguous() or shadow.numel() < adapters.master_extent:
+        raise ValueError('lora_merge: shadow must be a contiguous bf16 device buffer as long as the master')
+    if vout is not None:
+        _lora_check('lora_merge', adapters, (vout, adapters.master_extent, 'vout'))
+    _lib.call('da_lora_merge', master.data_ptr(), adapters.params.data_ptr(), adapters.table.data_ptr(), len(adapters.items),
+              adapters.tiles()[0], shadow.data_ptr(), vout.data_ptr() if vout is not None else 0, _stream())
+
+
+def lora_project(grad, adapters):
+    """adapters.grad <- (dA = s B^T dW, dB = s dW A^T) of every item from the dense weight gradient in ``grad``: one launch
+    that overwrites the adapter gradient buffer, every sum in a fixed order."""
+    _lora_check('lora_project', adapters, (grad, adapters.master_extent, 'grad'), (adapters.params, adapters.total, 'params'),
+                (adapters.grad, adapters.total, 'adapter grad'))
+    _, da, db = adapters.tiles()
+    _lib.call('da_lora_project', grad.data_ptr(), adapters.params.data_ptr(), adapters.table.data_ptr(),
+              len(adapters.items), da, db, adapters.grad.data_ptr(), _stream())

@@ -39,6 +39,59 @@ class FusedAdamW(torch.optim.Optimizer):
         self._gn = None                         # buffers of the norm pass (allocated on first use)
         self._gn_fresh = False                  # the record describes the gradient as it stands (trainer: shared pass)
         self._skipped_loaded = 0                # from a checkpoint, until the device record exists
+        self.lora = None                        # adapter mode (attach_lora): the LoRAAdapters this optimizer trains
+        self._lora_projected = False            # the adapter gradient has been projected from unet.grad this step
+
+    # ---- adapter mode ----------------------------------------------------------------------------------------------------
+    def attach_lora(self):
+        """Train the adapters ``unet.lora`` instead of the master.  step() then runs the projection (dA, dB from the dense
+        dW in ``unet.grad``), AdamW over the adapter buffers with the same hyper-parameters and grad_scale, the merge into
+        the shadows and refresh_transposed(); the norm pass, clipping and the non-finite guard work on the adapter gradient.
+        The master, its moments and ``unet.opt_step``'s meaning are untouched.  Not with EMA (it averages the frozen master),
+        not in step_range() slices."""
+        if self.unet.lora is None:
+            raise ValueError('attach_lora: the U-Net carries no adapters (UNetHIP.add_lora / load_lora first)')
+        if self.ema is not None:
+            raise ValueError('LoRA cannot be combined with EMA: the average is over the frozen master')
+        if self._gn is not None:   # the norm pass's tables describe the master's storages
+            self._skipped_loaded = self.last_grad_stats()['skipped_steps']
+            self._gn = None
+        self.lora = self.unet.lora
+        self._gn_fresh = self._lora_projected = False
+
+    def detach_lora(self):
+        if self._gn is not None:
+            self._skipped_loaded = self.last_grad_stats()['skipped_steps']
+            self._gn = None
+        self.lora = None
+        self._gn_fresh = self._lora_projected = False
+
+    def _lora_project(self):
+        if self.lora is not self.unet.lora:
+            raise RuntimeError('the adapters this optimizer trains are no longer attached to the U-Net')
+        if not self._lora_projected:
+            ops.lora_project(self.unet.grad, self.lora)
+            self._lora_projected = True
+
+    def _lora_step(self):
+        if self.ema is not None:
+            raise ValueError('LoRA cannot be combined with EMA: the average is over the frozen master')
+        if getattr(self, '_open', False):
+            raise RuntimeError('step_range() slices are not available while adapters are trained')
+        if self.device_scaled and not self._gn_fresh:
+            self.compute_grad_stats()
+        self._lora_project()
+        self._gn_fresh = self._lora_projected = False
+        g, u, l = self.param_groups[0], self.unet, self.lora
+        u.opt_step += 1
+        if self.device_scaled:
+            ops.adamw_dev(l.params, l.grad, l.exp_avg, l.exp_avg_sq, l.shadow_scratch, g['lr'], g['betas'][0], g['betas'][1],
+                          g['eps'], g['weight_decay'], u.opt_step, self._gn['stats'])
+        else:
+            ops.adamw(l.params, l.grad, l.exp_avg, l.exp_avg_sq, l.shadow_scratch, g['lr'], g['betas'][0], g['betas'][1],
+                      g['eps'], g['weight_decay'], u.opt_step, self.grad_scale)
+        ops.lora_merge(u.master, l, u.shadow)
+        u.refresh_transposed()
 
     # ---- gradient norm / clipping / non-finite guard -------------------------------------------------------------------
     @property
@@ -51,7 +104,10 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._gn is None:
             from . import ops
             u = self.unet
-            names, offs, numels, tables = u.grad_segments()
+            if self.lora is not None:   # one segment per adapter tensor of the adapter gradient buffer
+                names, tables = self.lora.sumsq_tables()
+            else:
+                names, offs, numels, tables = u.grad_segments()
             dev = u.grad.device
             stats = torch.zeros(ops.GRAD_STATS_WORDS, device=dev, dtype=torch.float32)
             if self._skipped_loaded:
@@ -69,7 +125,11 @@ class FusedAdamW(torch.optim.Optimizer):
         next step() reuses the record instead of running the pass again (the trainer's monitor and the clipper share it);
         call it only once the gradient is final."""
         gn = self._gn_buffers()
-        ops.segment_sumsq(self.unet.grad, gn['tables'], gn['partials'], gn['seg'], gn['stats'], self.grad_scale,
+        grad = self.unet.grad
+        if self.lora is not None:   # the trainable parameters' gradient: projected once per step, then measured
+            self._lora_project()
+            grad = self.lora.grad
+        ops.segment_sumsq(grad, gn['tables'], gn['partials'], gn['seg'], gn['stats'], self.grad_scale,
                           float(self.clip_max_norm or 0.0))
         self._gn_fresh = True
 
@@ -95,6 +155,8 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def begin_step(self):
         """Open optimizer step number opt_step+1; nothing updated yet."""
+        if self.lora is not None:
+            raise RuntimeError('step_range() slices are not available while adapters are trained')
         self.unet.opt_step += 1
         self._pending_hi = self.unet.master.numel()
         self._open = True
@@ -121,6 +183,8 @@ class FusedAdamW(torch.optim.Optimizer):
         gradient that launch writes nothing: weights, moments, shadow and EMA keep their bits and the device counter
         ``skipped_steps`` goes up by one.  The host step number (``unet.opt_step``, the bias correction) advances all the
         same - the host does not know, and must not wait to know, whether the device skipped."""
+        if self.lora is not None:
+            return self._lora_step()
         if self.device_scaled:
             if getattr(self, '_open', False):
                 raise RuntimeError('step_range() slices cannot be combined with clip_max_norm / guard_nonfinite')
@@ -155,6 +219,11 @@ class FusedAdamW(torch.optim.Optimizer):
             sd['ema_smoothing'] = self.ema_smoothing
         if self.device_scaled:
             sd['skipped_steps'] = self.last_grad_stats()['skipped_steps']
+        if self.lora is not None:
+            l = self.lora
+            sd['lora'] = {'rank': l.rank, 'alpha': l.alpha, 'target_modules': list(l.target_modules),
+                          'params': l.params.detach().cpu().clone(), 'exp_avg': l.exp_avg.detach().cpu().clone(),
+                          'exp_avg_sq': l.exp_avg_sq.detach().cpu().clone()}
         return sd
 
     def load_state_dict(self, sd):
@@ -171,3 +240,17 @@ class FusedAdamW(torch.optim.Optimizer):
             self._skipped_loaded = int(sd['skipped_steps'])
             if self._gn is not None:
                 self._gn['stats'][4:5].view(torch.int32).fill_(self._skipped_loaded)
+        if 'lora' in sd:
+            l, st = self.lora, sd['lora']
+            if l is None or (l.rank, list(l.target_modules)) != (st['rank'], list(st['target_modules'])) \
+                    or l.total != st['params'].numel():
+                raise ValueError('the checkpoint holds adapter state: attach matching adapters (same rank and targets) and '
+                                 'call attach_lora() before load_state_dict')
+            l.alpha = float(st['alpha'])
+            l.upload_table()
+            l.params.copy_(st['params'])
+            l.exp_avg.copy_(st['exp_avg'])
+            l.exp_avg_sq.copy_(st['exp_avg_sq'])
+            u.sync_shadows()
+        elif self.lora is not None:
+            raise ValueError('adapters are attached but the checkpoint holds no adapter state')

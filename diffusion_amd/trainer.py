@@ -166,6 +166,12 @@ class Trainer:
         for a in (algorithms or []):
             if hasattr(a, 'configure_optimizer'):
                 a.configure_optimizer(self.optimizer)
+        if getattr(self.optimizer, 'lora', None) is not None:
+            # adapters train from the whole exchanged dW (the projection is linear in it and runs after the exchange): one
+            # AdamW launch over the adapter buffers, no slices; EMA would average the frozen master
+            self.sliced_optimizer = False
+            if any(type(a).__name__ == 'EMA' for a in (algorithms or [])):
+                raise ValueError('LoRA cannot be combined with EMA: the average is over the frozen master')
         if getattr(self.optimizer, 'device_scaled', False) and self.sliced_optimizer:
             self.sliced_optimizer = False
             if self.rank == 0:

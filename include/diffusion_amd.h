@@ -566,6 +566,41 @@ int da_transpose_weight(const void* src, void* dst, int N, int T, int C, da_stre
 int da_transpose_weights_batched(const void* src_base, void* dst_base, const void* desc, int ntensors, int total_blocks,
                                  da_stream_t stream);
 
+/* ---- LoRA adapters on the merged-shadow path (csrc/lora.hip, diffusion_amd/lora.py) ----
+ *
+ * One adapted matrix: W [N][K] is a contiguous row range of a storage of the flat master / shadow / grad buffers (K = T C in
+ * the kernel layout of a weight, ld = K always), A [r][K] and B [N][r] live in a flat fp32 adapter buffer.  All offsets are
+ * 64-bit element counts from the bases (the flat fp32 buffer is 3.46 GB).  first_merge / first_da / first_db: the item's
+ * first workgroup in the three tile families, running sums in item order of
+ *   merge  ceil(N / 32) ceil(K / 128)      dA  ceil(r / 32) ceil(K / 128)      dB  ceil(N / 32)
+ * The host builds the table once and uploads it (ops.LoraTables checks every item against the buffers; the kernels trust
+ * it, as da_segment_sumsq trusts its tables).  1 <= r <= 128. */
+typedef struct DaLoraItem {
+  long long w_off, a_off, b_off;
+  int N, K, r;
+  float scale;
+  int first_merge, first_da, first_db, reserved;
+} DaLoraItem;
+
+/* shadow[w_off + n K + k] = bf16_rne(v), v = master[...] + scale * sum_j B[n][j] A[j][k] for every item, one launch.  The
+ * sum is an fp32 fmaf chain from 0 with j ascending (f32-input MFMA), then one fmaf onto the master value; a sum that is
+ * exactly 0 leaves v = the master value, so B = 0 reproduces da_cast_f32_bf16 bit for bit.  vout (may be NULL; may be
+ * master itself) receives the same v in fp32 at the same offsets: a master fused this way casts to these shadow bits.  Only
+ * elements of the items' row ranges are written.  Ragged tiles and an r that is odd or no multiple of the chunk are zero
+ * padded in LDS, never in memory.  DA_ERR_SHAPE (nothing launched) for n_items <= 0, total_tiles <= 0 (= the sum of the
+ * items' merge tiles), a NULL master / adapters / items / shadow, fp32 pointers not 4-byte or items not 8-byte aligned. */
+int da_lora_merge(const float* master, const float* adapters, const void* items, int n_items, int total_tiles,
+                  void* shadow, float* vout, da_stream_t stream);
+
+/* The adapter gradients from the dense weight gradient dW (fp32, at w_off of grad), one launch, OVERWRITING adapter_grad
+ * at the items' a_off / b_off:  dA[j][k] = scale * sum_n B[n][j] dW[n][k],  dB[n][j] = scale * sum_k dW[n][k] A[j][k].
+ * Since W' = W + scale B A this is exactly the chain rule.  Every output element is owned by one lane and is one fp32 fmaf
+ * chain from 0 over the ascending reduction index, times scale: no atomics, nothing depends on the grid or on
+ * "reserve_cus", two runs give identical bits.  tiles_da / tiles_db: the sums of the items' tiles of the two families.
+ * DA_ERR_SHAPE (nothing launched) for non-positive counts, a NULL pointer, adapter_grad == adapters, misaligned pointers. */
+int da_lora_project(const float* grad, const float* adapters, const void* items, int n_items, int tiles_da, int tiles_db,
+                    float* adapter_grad, da_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
