@@ -72,6 +72,10 @@ SIGNATURES = {
     'da_avgpool_global_f32': [_vp, _l, _fp, _l, _i, _i, _i, _vp],
     'da_inception_preprocess': [_vp, _i, _i, _i, _i, _vp, _vp],
     'da_feature_moments': [_fp, _l, _i, _i, _vp, _vp, _vp, _vp],
+    'da_fc_logits_f32': [_fp, _l, _fp, _fp, _l, _i, _i, _i, _vp],
+    'da_inception_score': [_fp, _l, _vp, _i, _i, _i, _vp, C.POINTER(_i), _vp],
+    'da_poly_mmd_workspace': [_i, _i],
+    'da_poly_mmd': [_fp, _l, _i, _fp, _l, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _l, _vp],
     'da_sampler_step': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_ms': [_fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
     'da_sampler_step_blend': [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _l, _i, _i, _i, _i, _vp],
@@ -97,7 +101,8 @@ SIGNATURES = {
     'da_lora_merge': [_fp, _fp, _vp, _i, _i, _vp, _fp, _vp],
     'da_lora_project': [_fp, _fp, _vp, _i, _i, _i, _fp, _vp],
 }
-_RESTYPES = {'da_norm_scratch_floats': C.c_long, 'da_segment_sumsq_scratch_floats': C.c_long}
+_RESTYPES = {'da_norm_scratch_floats': C.c_long, 'da_segment_sumsq_scratch_floats': C.c_long,
+             'da_poly_mmd_workspace': C.c_long}
 
 _lib = None
 

@@ -29,6 +29,10 @@ TARGET_ALIASES = {
     'torchmetrics.multimodal.CLIPScore': 'diffusion_amd.metrics.clip_score.CLIPScore',
     'torchmetrics.image.fid.FrechetInceptionDistance': 'diffusion_amd.metrics.fid.FrechetInceptionDistance',
     'torchmetrics.image.FrechetInceptionDistance': 'diffusion_amd.metrics.fid.FrechetInceptionDistance',
+    'torchmetrics.image.inception.InceptionScore': 'diffusion_amd.metrics.inception_score.InceptionScore',
+    'torchmetrics.image.InceptionScore': 'diffusion_amd.metrics.inception_score.InceptionScore',
+    'torchmetrics.image.kid.KernelInceptionDistance': 'diffusion_amd.metrics.kid.KernelInceptionDistance',
+    'torchmetrics.image.KernelInceptionDistance': 'diffusion_amd.metrics.kid.KernelInceptionDistance',
     'torch.optim.AdamW': 'diffusion_amd.optim.FusedAdamW',
 }
 TARGET_PREFIX_ALIASES = [

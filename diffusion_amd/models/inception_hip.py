@@ -13,8 +13,9 @@ documented behaviour; neither that package nor its weights file is available to 
 plain ``torch.nn`` module of the same definition (tests/inception_reference.py).
 
 State-dict keys are torchvision's, which are also those of torch-fidelity's ``pt_inception-2015-12-05`` file:
-``<unit>.conv.weight`` and ``<unit>.bn.{weight,bias,running_mean,running_var}``; ``fc.*`` and ``num_batches_tracked`` are
-ignored.
+``<unit>.conv.weight`` and ``<unit>.bn.{weight,bias,running_mean,running_var}``; ``num_batches_tracked`` and ``fc.bias``
+are ignored.  ``fc.weight`` ([1008, 2048]) is optional: when it is there the tower keeps it in fp32 for
+``logits_unbiased`` (torch-fidelity's bias-free head, ``da_fc_logits_f32``), which the Inception score reads.
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ from .vae_hip import _ohwi
 
 BN_EPS = 1e-3
 FEATURES = 2048
+CLASSES = 1008   # the 2015 graph's logits: 1000 ImageNet classes and 8 unused ones
 SIDE = ops.INCEPTION_SIDE
 
 
@@ -170,8 +172,16 @@ def random_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def random_fc_weight(seed: int = 0) -> torch.Tensor:
+    """the [1008, 2048] head of a random-init tower, N(0, 1 / 2048) from a generator of its own: ``random_state_dict`` draws
+    nothing for it and returns what it always did"""
+    g = torch.Generator().manual_seed(0x1008 + int(seed))
+    return torch.randn(CLASSES, FEATURES, generator=g) * FEATURES ** -0.5
+
+
 def check_state_dict(sd, where='state dict') -> None:
-    """strict: every key of every unit, with its shape; RuntimeError otherwise"""
+    """strict: every key of every unit, with its shape, and the shape of ``fc.weight`` when that is present; RuntimeError
+    otherwise"""
     missing, bad = [], []
     units = plan().units
     for key, shape in _state_keys(units):
@@ -179,6 +189,8 @@ def check_state_dict(sd, where='state dict') -> None:
             missing.append(key)
         elif tuple(sd[key].shape) != shape:
             bad.append((key, tuple(sd[key].shape), shape))
+    if 'fc.weight' in sd and tuple(sd['fc.weight'].shape) != (CLASSES, FEATURES):
+        bad.append(('fc.weight', tuple(sd['fc.weight'].shape), (CLASSES, FEATURES)))
     extra = [k for k in sd if k.split('.')[0] != 'fc' and not k.endswith('num_batches_tracked')
              and '.'.join(k.split('.')[:-2]) not in units]
     if missing or bad or extra:
@@ -218,6 +230,8 @@ class InceptionV3HIP:
             wf = (w * scale[:, None, None, None]).to(F32)
             bias = (bn['bias'] - bn['running_mean'] * scale).to(F32).contiguous()
             self.units[name] = (_ohwi(wf, cin_pad=cin), bias)
+        fc = state_dict.get('fc.weight')
+        self.fc_weight = None if fc is None else fc.detach().to(self.dev, F32).contiguous()
         self._bufs = {}   # batch size -> its buffers: a short last batch does not free and reallocate the full one's
 
     def _buffers(self, B):
@@ -250,6 +264,14 @@ class InceptionV3HIP:
         last = self.plan.blocks[-1]
         side = self.plan.bufs[last][0]
         return ops.avgpool_global_f32(bufs[last], bufs['feat'], B, side * side)
+
+    @torch.no_grad()
+    def logits_unbiased(self, features: torch.Tensor) -> torch.Tensor:
+        """fp32 [B, 1008]: ``features @ fc.weight.T`` without the bias (``da_fc_logits_f32``: float64 sums, one rounding)"""
+        if self.fc_weight is None:
+            raise RuntimeError("InceptionV3HIP.logits_unbiased: the state dict has no 'fc.weight'")
+        out = torch.empty(features.shape[0], CLASSES, device=self.dev, dtype=F32)
+        return ops.fc_logits_f32(features, self.fc_weight, out)
 
     @torch.no_grad()
     def __call__(self, images: torch.Tensor, trace: Optional[Callable] = None) -> torch.Tensor:

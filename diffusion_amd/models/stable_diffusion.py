@@ -102,7 +102,7 @@ class StableDiffusion(ComposerModel):
             loss_bins = [(0, 1)]
         self.val_guidance_scales = val_guidance_scales
         self.val_metrics = {}
-        metrics_to_sweep = ['FrechetInceptionDistance', 'InceptionScore', 'CLIPScore']
+        metrics_to_sweep = ['FrechetInceptionDistance', 'KernelInceptionDistance', 'InceptionScore', 'CLIPScore']
         for metric in val_metrics:
             name = metric.__class__.__name__
             if name in metrics_to_sweep:
@@ -348,6 +348,9 @@ class StableDiffusion(ComposerModel):
         elif isinstance(metric, MeanSquaredError):
             metric.update(outputs[0], outputs[1])
         elif metric.__class__.__name__ == 'FrechetInceptionDistance':
+            metric.update(batch[self.image_key], real=True)
+            metric.update(outputs[3][metric.guidance_scale], real=False)
+        elif metric.__class__.__name__ == 'KernelInceptionDistance':
             metric.update(batch[self.image_key], real=True)
             metric.update(outputs[3][metric.guidance_scale], real=False)
         elif metric.__class__.__name__ == 'InceptionScore':

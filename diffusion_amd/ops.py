@@ -747,6 +747,108 @@ def feature_moments(F, fsum, cov, n):
     _lib.call('da_feature_moments', F.data_ptr(), ldf, B, D, fsum.data_ptr(), cov.data_ptr(), n.data_ptr(), _stream())
 
 
+def _f32rows(x, name, cols=None):
+    """an fp32 device matrix with unit column stride -> (rows, columns, row stride)"""
+    if not isinstance(x, torch.Tensor) or x.dtype != F32:
+        raise TypeError(f'{name}: need an fp32 tensor, got {x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}')
+    if x.dim() != 2 or not x.is_cuda or x.stride(1) != 1 or x.shape[0] < 1 or (cols is not None and x.shape[1] != cols):
+        raise ValueError(f'{name}: need an fp32 [rows, {cols if cols is not None else "cols"}] device matrix with unit column '
+                         f'stride, got {tuple(x.shape)} strides {x.stride()} on {x.device}')
+    return x.shape[0], x.shape[1], max(x.stride(0), x.shape[1])
+
+
+def fc_logits_f32(F, W, out):
+    """``da_fc_logits_f32``: out[b, c] = sum_k F[b, k] W[c, k] in float64, rounded once to fp32 (no bias).  F fp32 [B, K] and
+    out fp32 [B, C] with unit column stride (row strides free), W contiguous fp32 [C, K]; K % 4 == 0."""
+    B, K, ldf = _f32rows(F, 'fc_logits_f32: F')
+    C, _, _ = _f32rows(W, 'fc_logits_f32: W', K)
+    _, _, ldo = _f32rows(out, 'fc_logits_f32: out', C)
+    if out.shape[0] != B or not W.is_contiguous():
+        raise ValueError(f'fc_logits_f32: F {tuple(F.shape)}, W {tuple(W.shape)} (contiguous), out {tuple(out.shape)}')
+    if K % 4 or ldf % 4 or F.data_ptr() % 16 or W.data_ptr() % 16:
+        raise ValueError('fc_logits_f32: K % 4 == 0, F row stride % 4 == 0 and 16-byte aligned F and W are required')
+    _lib.call('da_fc_logits_f32', F.data_ptr(), ldf, W.data_ptr(), out.data_ptr(), ldo, B, K, C, _stream())
+    return out
+
+
+def _host_indices(idx, name):
+    """the host copy of an index tensor: int32, on the CPU (the checks below read it without a device synchronisation)"""
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+        raise TypeError(f'{name}: need an int32 tensor, got {idx.dtype if isinstance(idx, torch.Tensor) else type(idx).__name__}')
+    if idx.is_cuda:
+        raise ValueError(f'{name}: pass the HOST tensor; it is range-checked here and uploaded afterwards')
+    return idx.contiguous()
+
+
+def inception_score(logits, perm, splits, scores=None):
+    """``da_inception_score``: per-chunk Inception scores of rows ``perm`` of logits fp32 [N, C] (unit column stride, row
+    stride free), chunked as ``torch.chunk(splits)`` does.  ``perm``: int32 [N] on the HOST; it must be a permutation of
+    range(N) - checked here, before the upload, so that no out-of-range row reaches a launch.  Returns the float64 device
+    vector of the chunks produced (a view of ``scores`` [splits] when that is given)."""
+    N, C, ld = _f32rows(logits, 'inception_score: logits')
+    perm = _host_indices(perm, 'inception_score: perm')
+    if isinstance(splits, bool) or not isinstance(splits, int) or splits < 1:
+        raise ValueError(f'inception_score: splits must be a positive int, got {splits!r}')
+    if perm.dim() != 1 or perm.numel() != N or not torch.equal(perm.sort().values, torch.arange(N, dtype=torch.int32)):
+        raise ValueError(f'inception_score: perm must be a permutation of range({N})')
+    if not 1 <= C <= 4096:
+        raise ValueError(f'inception_score: 1 <= C <= 4096, got {C}')
+    if scores is None:
+        scores = torch.empty(splits, device=logits.device, dtype=torch.float64)
+    elif not isinstance(scores, torch.Tensor) or scores.dtype != torch.float64 or not scores.is_cuda \
+            or not scores.is_contiguous() or tuple(scores.shape) != (splits,):
+        raise ValueError(f'inception_score: scores must be a contiguous float64 device tensor [{splits}]')
+    chunks = ctypes.c_int(0)
+    dperm = perm.to(logits.device)
+    _lib.call('da_inception_score', logits.data_ptr(), ld, dperm.data_ptr(), N, C, splits, scores.data_ptr(),
+              ctypes.byref(chunks), _stream())
+    return scores[:chunks.value]
+
+
+def poly_mmd_workspace(subsets: int, m: int) -> int:
+    """``da_poly_mmd_workspace``: float64 elements of workspace ``poly_mmd`` needs (0: the pair is rejected)"""
+    return int(_lib.load().da_poly_mmd_workspace(int(subsets), int(m)))
+
+
+def poly_mmd(Fr, Ff, idx_r, idx_f, degree=3, gamma=None, coef=1.0, out=None, ws=None):
+    """``da_poly_mmd``: the polynomial-kernel MMD of torchmetrics' KID per subset.  Fr fp32 [Nr, D], Ff fp32 [Nf, D] (unit column
+    stride, row stride % 4 == 0); idx_r, idx_f int32 [subsets, m] on the HOST, range-checked here before the upload;
+    ``gamma=None`` is 1 / D.  Returns out, float64 [subsets] on the device."""
+    Nr, D, ldr = _f32rows(Fr, 'poly_mmd: Fr')
+    Nf, _, ldf = _f32rows(Ff, 'poly_mmd: Ff', D)
+    idx_r, idx_f = _host_indices(idx_r, 'poly_mmd: idx_r'), _host_indices(idx_f, 'poly_mmd: idx_f')
+    if idx_r.dim() != 2 or idx_r.shape != idx_f.shape or idx_r.shape[0] < 1:
+        raise ValueError(f'poly_mmd: idx_r {tuple(idx_r.shape)} and idx_f {tuple(idx_f.shape)} must both be [subsets, m]')
+    subsets, m = idx_r.shape
+    for idx, n, nm in ((idx_r, Nr, 'idx_r'), (idx_f, Nf, 'idx_f')):
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise ValueError(f'poly_mmd: {nm} must lie in [0, {n})')
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= 8:
+        raise ValueError(f'poly_mmd: degree must be an int in 1..8, got {degree!r}')
+    gamma = 1.0 / D if gamma is None else float(gamma)
+    coef = float(coef)
+    need = poly_mmd_workspace(subsets, m)
+    if m < 2 or need == 0:
+        raise ValueError(f'poly_mmd: need 2 <= m <= 65536 and subsets <= 65535, got m = {m}, subsets = {subsets}')
+    if not (0.0 < gamma < float('inf')) or not (0.0 <= coef < float('inf')):
+        raise ValueError(f'poly_mmd: gamma must be > 0 and coef >= 0, got {gamma}, {coef}')
+    if D % 4 or ldr % 4 or ldf % 4 or Fr.data_ptr() % 16 or Ff.data_ptr() % 16:
+        raise ValueError('poly_mmd: D % 4 == 0, row strides % 4 == 0 and 16-byte aligned stores are required')
+    f64 = dict(device=Fr.device, dtype=torch.float64)
+    if out is None:
+        out = torch.empty(subsets, **f64)
+    if ws is None:
+        ws = torch.empty(need, **f64)
+    for z, nm, n, exact in ((out, 'out', subsets, True), (ws, 'ws', need, False)):
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.float64 or not z.is_cuda or not z.is_contiguous() \
+                or z.dim() != 1 or z.numel() < n or (exact and z.numel() != n):
+            raise ValueError(f'poly_mmd: {nm} must be a contiguous float64 device vector of {"" if exact else ">= "}{n}')
+    dr, df = idx_r.to(Fr.device), idx_f.to(Fr.device)
+    _lib.call('da_poly_mmd', Fr.data_ptr(), ldr, Nr, Ff.data_ptr(), ldf, Nf, dr.data_ptr(), df.data_ptr(), subsets, m, D,
+              degree, gamma, coef, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
 def _rescale_operands(fn, factor, HW, npix):
     """``factor=`` / ``HW=`` of the four step wrappers (guidance rescale): the sample's pixel count, checked."""
     if HW is None or int(HW) < 1 or npix % int(HW):

@@ -38,8 +38,9 @@ def train(config) -> None:
     )
 
     # evaluation data (reference train.py:44-63): a plain `dataset.eval_dataset` is built like the train loader with the
-    # per-rank share of `eval_batch_size`, and a `CLIPScore` or `FrechetInceptionDistance` in the model's `val_metrics` scores what it
-    # generates; the Evaluator objects of `dataset.evaluators` and the Inception score are out of scope
+    # per-rank share of `eval_batch_size`, and a `CLIPScore`, `FrechetInceptionDistance`, `InceptionScore` or
+    # `KernelInceptionDistance` in the model's `val_metrics` scores what it generates; the Evaluator objects of
+    # `dataset.evaluators` are out of scope
     eval_dataloader = None
     ds = config.dataset
     if 'eval_dataset' in ds and ds.eval_dataset and '_target_' in ds.eval_dataset:

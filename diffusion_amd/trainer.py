@@ -116,6 +116,14 @@ class OptimizerMonitor(Callback):
             trainer.log({f'l2_norm/grad/{k}': v for k, v in trainer.optimizer.last_segment_norms().items()})
 
 
+def _metric_log_entries(name, result):
+    """what ``Trainer.eval`` logs for one metric: ``metrics/eval/<name>`` for a scalar; for a (mean, std) pair (``InceptionScore``,
+    ``KernelInceptionDistance``) the mean under that key and the std under ``metrics/eval/<name>-std``"""
+    if isinstance(result, (tuple, list)) and len(result) == 2:
+        return {f'metrics/eval/{name}': float(result[0]), f'metrics/eval/{name}-std': float(result[1])}
+    return {f'metrics/eval/{name}': float(result)}
+
+
 class Trainer:
 
     def __init__(self, model, train_dataloader: Iterable, optimizers=None, max_duration='1ba',
@@ -386,8 +394,10 @@ class Trainer:
         logged as ``metrics/eval/<name>``.  A ``CLIPScore`` among the validation metrics (metrics/clip_score.py) is fed the
         images ``eval_forward`` generates per entry of ``val_guidance_scales`` and reduces its own two-float state over the
         ranks in ``compute()``; a ``FrechetInceptionDistance`` (metrics/fid.py) is fed the batch's real images and the
-        generated ones per guidance scale and reduces its float64 feature moments the same way (the Inception score stays out
-        of scope).  Callbacks get ``eval_batch_end`` after each batch's metric updates.  Nothing collective runs before the final
+        generated ones per guidance scale and reduces its float64 feature moments the same way; a ``KernelInceptionDistance``
+        (metrics/kid.py) is fed like the FID and an ``InceptionScore`` (metrics/inception_score.py) the generated images, both
+        gather their per-image stores over the ranks in ``compute()`` and return (mean, std), logged as ``metrics/eval/<name>``
+        and ``metrics/eval/<name>-std``.  Callbacks get ``eval_batch_end`` after each batch's metric updates.  Nothing collective runs before the final
         reduction, so the ranks may see different numbers of batches (the COCO loader's unpadded partition).  With no eval
         dataloader this returns {}."""
         if self.eval_dataloader is None:
@@ -416,7 +426,7 @@ class Trainer:
                 dist.all_reduce(st)
                 out[f'metrics/eval/{name}'] = float((st[0] / st[1]).item())
             else:
-                out[f'metrics/eval/{name}'] = float(m.compute())
+                out.update(_metric_log_entries(name, m.compute()))
         self.log(out)
         return out
 

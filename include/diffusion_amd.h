@@ -555,6 +555,39 @@ int da_inception_preprocess(const void* src, int src_kind, int B, int H, int W, 
  * no atomics, identical bits run to run.  D % 8 == 0, D <= 16384. */
 int da_feature_moments(const float* F, long ldf, int B, int D, double* sum, double* cov, double* n, da_stream_t stream);
 
+/* torch-fidelity's `logits_unbiased` head of the FID Inception (F.linear(features, fc.weight), no bias), which
+ * torchmetrics' InceptionScore(feature='logits_unbiased') runs: out[b][c] = sum_k F[b][k] W[c][k].  F fp32 [B][K] (rows of
+ * ldf floats, ldf % 4 == 0), W fp32 [C][K] contiguous, out fp32 [B][C] (rows of ldo >= C floats); F and W 16-byte aligned.
+ * The sum is float64 FMAs in an order fixed by K alone, rounded once to fp32.  K % 4 == 0, any C >= 1. */
+int da_fc_logits_f32(const float* F, long ldf, const float* W, float* out, long ldo, int B, int K, int C,
+                     da_stream_t stream);
+
+/* torchmetrics' InceptionScore.compute() after its permutation: rows perm[0..N) of logits fp32 [.][C] (rows of ld floats;
+ * the row offset perm[i] * ld is 64-bit) are cut as torch.chunk(splits) does - chunks of ceil(N / splits) rows, the last
+ * may be short and there may be fewer than `splits` - and per chunk p = softmax(row) (float64 log-softmax with the
+ * maximum subtracted), m = mean_i p_i, score = exp(mean_i sum_c p_ic (log p_ic - log m_c)); terms with p_ic == 0 are 0.
+ * scores float64 [splits] in device memory, the first *chunks entries are written; *chunks (host memory) is set before
+ * returning.  perm int32 [N] in device memory, every entry a valid row: the caller checks that.  1 <= C <= 4096.  Fixed
+ * summation order, no atomics. */
+int da_inception_score(const float* logits, long ld, const int* perm, int N, int C, int splits, double* scores, int* chunks,
+                       da_stream_t stream);
+
+/* the number of float64 elements da_poly_mmd needs in ws for (subsets, m); 0 for a pair it rejects */
+long da_poly_mmd_workspace(int subsets, int m);
+
+/* torchmetrics' KernelInceptionDistance.compute() per subset (poly_mmd of poly_kernel blocks): with x_i = Fr[idx_r[s][i]],
+ * y_j = Ff[idx_f[s][j]] and k(a, b) = (gamma <a, b> + coef)^degree,
+ *   out[s] = (sum_{i != j} k(x_i, x_j) + sum_{i != j} k(y_i, y_j)) / (m (m - 1)) - 2 sum_{i, j} k(x_i, y_j) / m^2.
+ * Fr fp32 [Nr][D], Ff fp32 [Nf][D] (rows of ldr / ldf floats, multiples of 4, 16-byte aligned bases; row offsets are
+ * 64-bit), idx_r, idx_f int32 [subsets][m] in device memory with 0 <= idx < Nr / Nf: the caller checks that.  Dot products
+ * and sums are float64 (v_mfma_f64_16x16x4_f64 over rows gathered into LDS, no gathered copy in memory); the diagonal is
+ * skipped, not subtracted; per-tile sums go to ws and are added in tile order: identical bits run to run.  out float64
+ * [subsets].  2 <= m <= 65536, subsets <= 65535, D % 4 == 0, 1 <= degree <= 8, gamma > 0, coef >= 0,
+ * ws_doubles >= da_poly_mmd_workspace(subsets, m). */
+int da_poly_mmd(const float* Fr, long ldr, int Nr, const float* Ff, long ldf, int Nf, const int* idx_r, const int* idx_f,
+                int subsets, int m, int D, int degree, double gamma, double coef, double* out, double* ws, long ws_doubles,
+                da_stream_t stream);
+
 int da_cast_f32_bf16(const float* src, void* dst, long n, da_stream_t stream);
 
 /* dst[c][T-1-t][n] = src[n][t][c]: the weight layout da_gemm_nt needs for dgrad */
