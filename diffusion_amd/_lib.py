@@ -63,6 +63,7 @@ SIGNATURES = {
     'da_add_noise_ex': [_fp, _fp, _vp, _i, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _vp],
     'da_image_ingest': [_vp, _vp, _vp, _i, _i, _vp, _i, _vp],
     'da_image_ingest_rect': [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
+    'da_image_ingest_aug': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
     'da_image_resize': [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp],
     'da_clip_preprocess': [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _fp, _fp, _vp, _i, _vp],
     'da_clip_score': [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _vp],

@@ -22,6 +22,13 @@
 // nw = floor(Rh w / h)), so nw >= Rw and nh >= Rh and the centre crop lies inside the resized image.  At Rh == Rw the test
 // is w <= h and the rule is LargestCenterSquare's: da_image_ingest is the same kernel with Rh = Rw = R.
 //
+// da_image_ingest_aug: the same cover-resize with the crop window and a horizontal flip chosen per image, aug[b] = (top,
+// left, flip) in resized-image pixels: out[Y][X] = resized[top + Y][c] with c = left + X, or c = nw - 1 - (left + X) when
+// flip = 1 (the crop at `left` of the mirrored image).  Only the index handed to axis_setup changes, so both passes are
+// the ones above.  The kernel clamps top into [0, nh - Rh] and left into [0, nw - Rw]; no table can move a tap outside its
+// image.  A flipped column has the mirrored taps with the same integer weights (num changes sign, |num| does not), and the
+// horizontal sums are integers exact in fp64, so flip = 1 gives bit for bit what the mirrored source gives without it.
+//
 // da_image_resize: the same kernel with three independent switches (the COCO evaluation loader's transforms).
 // geometry 1 stretches instead: nw = Rw, nh = Rh, crop origin 0, each axis resized on its own.  range 1 writes v / 255
 // (ToTensor alone) instead of v / 127.5 - 1.  filter 1 is the two-tap bilinear of F.interpolate(align_corners=False,
@@ -80,12 +87,13 @@ DEVINL void axis_setup_two_tap(int n_in, int n_out, int i, int* lo_, int* hi_, i
   *inv_ = 1.0 / (double)(two ? d : d - r);
 }
 
-__global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const unsigned char* __restrict__ src,
-                                                                          const long long* __restrict__ off,
-                                                                          const int* __restrict__ hw, int Rh, int Rw,
-                                                                          int tiles_y, int tiles_x,
-                                                                          void* __restrict__ out, int kind, int geometry,
-                                                                          int filter, int range) {
+// One body for every entry.  AUG = false is the centre crop (da_image_ingest, da_image_ingest_rect, da_image_resize); AUG = true
+// takes the crop origin and a horizontal flip per image from aug[b] = (top, left, flip), in resized-image pixels (see the
+// header comment).  The switch is a template argument: the centre-crop kernel carries no trace of the other.
+template <bool AUG>
+DEVINL void image_ingest_body(const unsigned char* __restrict__ src, const long long* __restrict__ off,
+                              const int* __restrict__ hw, const int* __restrict__ aug, int Rh, int Rw, int tiles_y,
+                              int tiles_x, void* __restrict__ out, int kind, int geometry, int filter, int range) {
   __shared__ int s_lo[2][IMG_TILE], s_hi[2][IMG_TILE], s_num[2][IMG_TILE];
   __shared__ double s_inv[2][IMG_TILE];
   __shared__ float s_row[IMG_TILE][IMG_TILE][3];
@@ -99,11 +107,21 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
   const bool fit_w = w * Rh <= h * Rw;
   const int nw = geometry || fit_w ? Rw : (int)((long long)Rh * w / h);
   const int nh = geometry ? Rh : fit_w ? (int)((long long)Rw * h / w) : Rh;
-  const int qy = (nh - Rh) >> 1, qx = (nw - Rw) >> 1;
-  const int top = ((nh - Rh) & 1) ? qy + (qy & 1) : qy, left = ((nw - Rw) & 1) ? qx + (qx & 1) : qx;
+  int top, left, flip = 0;
+  if (AUG) {   // the caller's origins, clamped into [0, n - R]: whatever aug holds, every tap stays inside the image
+    top = min(max(aug[3 * b], 0), nh - Rh);
+    left = min(max(aug[3 * b + 1], 0), nw - Rw);
+    flip = aug[3 * b + 2];
+    if (flip & ~1) return;   // not 0 or 1: the image is skipped like an oversized one (uniform over the block, no barrier yet)
+  } else {
+    const int qy = (nh - Rh) >> 1, qx = (nw - Rw) >> 1;
+    top = ((nh - Rh) & 1) ? qy + (qy & 1) : qy;
+    left = ((nw - Rw) & 1) ? qx + (qx & 1) : qx;
+  }
   if (t < 2 * IMG_TILE) {
     const int a = t >> 4, j = t & (IMG_TILE - 1);   // a = 0: columns, 1: rows; indices past the target repeat the last one
-    const int i = a ? min(ty0 + j, Rh - 1) + top : min(tx0 + j, Rw - 1) + left;
+    int i = a ? min(ty0 + j, Rh - 1) + top : min(tx0 + j, Rw - 1) + left;
+    if (AUG && !a && flip) i = nw - 1 - i;   // the crop at `left` of the mirrored image: resized column nw - 1 - (left + X)
     if (filter)
       axis_setup_two_tap(a ? h : w, a ? nh : nw, i, &s_lo[a][j], &s_hi[a][j], &s_num[a][j], &s_inv[a][j]);
     else
@@ -173,8 +191,27 @@ __global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const 
   }
 }
 
-int launch_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
-                  int out_kind, int geometry, int filter, int range, hipStream_t s) {
+__global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_kernel(const unsigned char* __restrict__ src,
+                                                                          const long long* __restrict__ off,
+                                                                          const int* __restrict__ hw, int Rh, int Rw,
+                                                                          int tiles_y, int tiles_x,
+                                                                          void* __restrict__ out, int kind, int geometry,
+                                                                          int filter, int range) {
+  image_ingest_body<false>(src, off, hw, nullptr, Rh, Rw, tiles_y, tiles_x, out, kind, geometry, filter, range);
+}
+
+__global__ __launch_bounds__(IMG_TILE* IMG_TILE) void image_ingest_aug_kernel(const unsigned char* __restrict__ src,
+                                                                              const long long* __restrict__ off,
+                                                                              const int* __restrict__ hw,
+                                                                              const int* __restrict__ aug, int Rh, int Rw,
+                                                                              int tiles_y, int tiles_x,
+                                                                              void* __restrict__ out, int kind) {
+  image_ingest_body<true>(src, off, hw, aug, Rh, Rw, tiles_y, tiles_x, out, kind, 0, 0, 0);
+}
+
+// aug == nullptr: the centre-crop kernel; else the per-image crop / flip kernel (geometry, filter, range are then 0)
+int launch_ingest(const unsigned char* src, const long long* off, const int* hw, const int* aug, int B, int Rh, int Rw,
+                  void* out, int out_kind, int geometry, int filter, int range, hipStream_t s) {
   DA_CLEAR_ERR();
   if ((geometry | filter | range) & ~1) return DA_ERR_SHAPE;
   if (B < 1 || Rh < 1 || Rh > 4096 || Rw < 1 || Rw > 4096 || (out_kind != 0 && out_kind != 1) || !src || !off || !hw ||
@@ -185,8 +222,12 @@ int launch_ingest(const unsigned char* src, const long long* off, const int* hw,
   const int tiles_y = (Rh + IMG_TILE - 1) / IMG_TILE, tiles_x = (Rw + IMG_TILE - 1) / IMG_TILE;
   const long blocks = (long)B * tiles_y * tiles_x;
   if (blocks > 0x7fffffffL) return DA_ERR_SHAPE;
-  hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, Rh, Rw,
-                     tiles_y, tiles_x, out, out_kind, geometry, filter, range);
+  if (aug)
+    hipLaunchKernelGGL(image_ingest_aug_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, aug,
+                       Rh, Rw, tiles_y, tiles_x, out, out_kind);
+  else
+    hipLaunchKernelGGL(image_ingest_kernel, dim3((unsigned)blocks), dim3(IMG_TILE * IMG_TILE), 0, s, src, off, hw, Rh, Rw,
+                       tiles_y, tiles_x, out, out_kind, geometry, filter, range);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -195,15 +236,21 @@ int launch_ingest(const unsigned char* src, const long long* off, const int* hw,
 
 extern "C" int da_image_ingest(const unsigned char* src, const long long* off, const int* hw, int B, int R, void* out,
                                int out_kind, hipStream_t s) {
-  return launch_ingest(src, off, hw, B, R, R, out, out_kind, 0, 0, 0, s);
+  return launch_ingest(src, off, hw, nullptr, B, R, R, out, out_kind, 0, 0, 0, s);
 }
 
 extern "C" int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw,
                                     void* out, int out_kind, hipStream_t s) {
-  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, 0, 0, 0, s);
+  return launch_ingest(src, off, hw, nullptr, B, Rh, Rw, out, out_kind, 0, 0, 0, s);
 }
 
 extern "C" int da_image_resize(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw,
                                void* out, int out_kind, int geometry, int filter, int range, hipStream_t s) {
-  return launch_ingest(src, off, hw, B, Rh, Rw, out, out_kind, geometry, filter, range, s);
+  return launch_ingest(src, off, hw, nullptr, B, Rh, Rw, out, out_kind, geometry, filter, range, s);
+}
+
+extern "C" int da_image_ingest_aug(const unsigned char* src, const long long* off, const int* hw, const int* aug, int B,
+                                   int Rh, int Rw, void* out, int out_kind, hipStream_t s) {
+  if (!aug) return DA_ERR_SHAPE;
+  return launch_ingest(src, off, hw, aug, B, Rh, Rw, out, out_kind, 0, 0, 0, s);
 }

@@ -108,7 +108,9 @@ class collate_raw_images:
     ``(Rh, Rw)`` tuple for a rectangular target.  The packed tensor is allocated pinned when ``pin_memory`` is set (and a
     device is present), so the training step's upload is asynchronous without a second host copy.  ``image_transform``
     (the COCO evaluation loader's) rides along as ``batch['image_transform']``: a dict of the ``ops.image_resize`` switches
-    ``geometry`` / ``filter`` / ``range``; without one the key is absent and the batch means the training transform."""
+    ``geometry`` / ``filter`` / ``range``; without one the key is absent and the batch means the training transform.
+    Samples of a bucketed run (``datasets/buckets.py``) carry ``image_target``, their bucket: the batch's one bucket becomes
+    its ``image_size``; their ``image_aug`` draws are stacked to int32 ``[B, 3]`` like any other key."""
 
     def __init__(self, image_size=0, pin_memory: bool = False, image_transform=None):
         self.image_size = target_hw(image_size) if hasattr(image_size, '__len__') else int(image_size)
@@ -122,6 +124,12 @@ class collate_raw_images:
         batch['image_raw'], batch['image_off'], batch['image_hw'] = raw, off, hw
         if self.image_size:
             batch['image_size'] = self.image_size
+        if 'image_target' in batch:   # a bucketed run (datasets/buckets.py): the batch's one bucket is its target
+            t = batch.pop('image_target')
+            if not bool((t == t[0]).all()):
+                raise ValueError(f'a batch mixes the targets {sorted({tuple(r) for r in t.tolist()})}: bucketed samples '
+                                 'need AspectBucketBatchSampler')
+            batch['image_size'] = (int(t[0, 0]), int(t[0, 1]))
         if self.image_transform is not None:
             batch['image_transform'] = dict(self.image_transform)
         return batch
@@ -143,7 +151,8 @@ def is_raw_image_directory(directory: str, resize_size) -> bool:
 def ingest_batch(batch, R, kind: int, device, transform=None):
     """Upload a raw batch (non-blocking) and run the ingest kernel for the target ``R``, an int or an ``(Rh, Rw)`` pair:
     kind 0 -> bf16 [B*Rh*Rw, 8], kind 1 -> fp32 [B,3,Rh,Rw].  An int runs the square entry, a pair the rectangular one;
-    with a ``transform`` (a batch's ``image_transform``) ``ops.image_resize`` runs with its switches instead."""
+    with a ``transform`` (a batch's ``image_transform``) ``ops.image_resize`` runs with its switches instead, and a batch
+    that carries ``image_aug`` (int32 [B, 3]: crop origin and flip per image) goes through ``ops.image_ingest_aug``."""
     from .. import ops
     raw, off, hw = (batch[k] for k in RAW_KEYS)
     if off.is_cuda or hw.is_cuda:
@@ -156,7 +165,15 @@ def ingest_batch(batch, R, kind: int, device, transform=None):
         out = torch.empty(B * Rh * Rw, 8, device=device, dtype=torch.bfloat16)
     else:
         out = torch.empty(B, 3, Rh, Rw, device=device, dtype=torch.float32)
-    if transform is not None:
+    aug = batch.get('image_aug')
+    if aug is not None:   # per-image crop origin and flip (datasets/buckets.py draws them): the augmenting entry
+        if transform is not None:
+            raise ValueError('ingest_batch: image_aug and image_transform cannot be combined')
+        if aug.is_cuda:
+            raise ValueError('ingest_batch: image_aug must still be a host tensor (its origins are checked on it)')
+        aug = aug.to(torch.int32).contiguous()
+        ops.image_ingest_aug(d_raw, d_off, d_hw, aug.to(device, non_blocking=True), Rh, Rw, out, kind, host=(off, hw, aug))
+    elif transform is not None:
         ops.image_resize(d_raw, d_off, d_hw, Rh, Rw, out, kind, *(int(transform[k]) for k in TRANSFORM_KEYS), host=(off, hw))
     elif isinstance(R, int):
         ops.image_ingest(d_raw, d_off, d_hw, R, out, kind, host=(off, hw))

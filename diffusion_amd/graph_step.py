@@ -38,7 +38,10 @@ class GraphedMicrobatch:
         self.noise = torch.empty(latents.shape, device=dev, dtype=torch.float32)
         self.lat.copy_(latents)
         self.cond.copy_(cond)
-        self.noise.normal_()
+        # placeholder noise for the warm-up and the capture, from a generator of its own: a capture must not advance the global
+        # stream the eager path draws from (a run over aspect-ratio buckets captures whenever a new shape turns up, and every
+        # draw after it would differ from the eager run's)
+        self.noise.normal_(generator=torch.Generator(device=dev).manual_seed(0))
         self.graph = torch.cuda.CUDAGraph()
         # warm-up on a side stream (lazy one-time work - scratch buffers, split-K workspace, hipFuncSetAttribute, the
         # transposed-weight descriptor table - must not happen inside the capture); its gradient contribution is undone
@@ -84,6 +87,7 @@ class GraphStepCache:
         self.model = model
         self.max_graphs = max_graphs
         self.graphs: Dict[Tuple, GraphedMicrobatch] = {}
+        self.captures = 0   # graphs captured so far (a run with more shapes than max_graphs keeps re-capturing)
 
     def usable(self, batch) -> bool:
         """Only latent-space models with precomputed latents are captured: a model without them (PixelDiffusion encodes
@@ -114,6 +118,9 @@ class GraphStepCache:
             noise = torch.randn(lat.shape, device=dev, dtype=lat.dtype if lat.is_floating_point() else torch.float32)
         if g is None:
             if len(self.graphs) >= self.max_graphs:
-                self.graphs.pop(next(iter(self.graphs)))
+                self.graphs.pop(next(iter(self.graphs)))   # the least recently replayed one
             g = self.graphs[key] = GraphedMicrobatch(m, lat, cond, weight)
+            self.captures += 1
+        else:   # a bucketed run alternates shapes: keep the ones in use, evict by last use and not by age
+            self.graphs[key] = self.graphs.pop(key)
         return g.replay(lat, cond, t, noise)

@@ -158,7 +158,8 @@ class StableDiffusion(ComposerModel):
         [B, 3, Rh, Rw].  One non-blocking upload of the bytes and one kernel (``ops.image_ingest``, or
         ``ops.image_ingest_rect`` for a rectangular target): the reference's LargestCenterSquare -> ToTensor -> Normalize
         (laion.py:159-164).  The target is the batch's ``image_size`` (what the dataloader was built with: an int, or an
-        ``(Rh, Rw)`` pair), else ``unet.config.sample_size * 8``.
+        ``(Rh, Rw)`` pair; in a bucketed run the batch's bucket), else ``unet.config.sample_size * 8``.  A batch that carries
+        ``image_aug`` (crop origin and flip per image, ``datasets/buckets.py``) goes through ``ops.image_ingest_aug``.
 
         A batch with an ``image_transform`` (the COCO evaluation loader's: the ``ops.image_resize`` switches) always becomes
         the fp32 ``image`` [B, 3, Rh, Rw] in [0, 1], HIP VAE or not: ``eval_forward`` reads its size to generate at and
@@ -171,7 +172,7 @@ class StableDiffusion(ComposerModel):
         transform = batch.get('image_transform')
         hip = getattr(self, 'vae_hip', None) is not None and transform is None
         out = ingest_batch(batch, R, 0 if hip else 1, self.unet.device_, transform)
-        rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k not in ('image_size', 'image_transform')}
+        rest = {k: v for k, v in batch.items() if k not in RAW_KEYS and k not in ('image_size', 'image_transform', 'image_aug')}
         rest['image_nhwc8' if hip else self.image_key] = out.view(-1, Rh, Rw, 8) if hip else out
         return rest
 

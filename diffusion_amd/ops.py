@@ -586,6 +586,37 @@ def image_ingest_rect(raw, off, hw, Rh, Rw, out, kind, host=None):
               _stream())
 
 
+def image_ingest_aug(raw, off, hw, aug, Rh, Rw, out, kind, host=None):
+    """``image_ingest_rect`` with a crop window and a horizontal flip per image (``da_image_ingest_aug``).  ``aug`` int32
+    [B, 3] = (top, left, flip), a contiguous device tensor: origins in pixels of the resized image (``ingest_geometry``'s
+    ``nh x nw``), ``out[Y][X] = resized[top + Y][left + X]``, and with ``flip = 1`` the same crop of the mirrored image.
+    ``host = (off, hw, aug)``: on these copies the buffer bounds, ``0 <= top <= nh - Rh``, ``0 <= left <= nw - Rw`` and
+    ``flip in {0, 1}`` are checked before anything is launched (the kernel clamps the origins besides).  The centre origins
+    with flip 0 give ``image_ingest_rect``'s bits."""
+    Rh, Rw = int(Rh), int(Rw)
+    if host is None or len(host) != 3:
+        raise ValueError('image_ingest_aug: host=(off, hw, aug) copies of the tables are required for the bounds check')
+    B = _image_ingest_args('image_ingest_aug', raw, off, hw, Rh, Rw, out, kind, host[:2])
+    if not isinstance(aug, torch.Tensor) or not aug.is_cuda or aug.dtype != torch.int32 or not aug.is_contiguous() \
+            or tuple(aug.shape) != (B, 3):
+        raise ValueError('image_ingest_aug: aug int32 [B, 3] must be a contiguous device tensor')
+    h_aug = torch.as_tensor(host[2])
+    if h_aug.is_cuda or tuple(h_aug.shape) != (B, 3):
+        raise ValueError('image_ingest_aug: host aug [B, 3] must be a host tensor')
+    h_aug, h_hw = h_aug.to(torch.int64), torch.as_tensor(host[1]).to(torch.int64)
+    h, w = h_hw[:, 0], h_hw[:, 1]
+    fit_w = w * Rh <= h * Rw   # ingest_geometry's cover rule, on the whole batch
+    nw = torch.where(fit_w, torch.full_like(w, Rw), (Rh * w) // h)
+    nh = torch.where(fit_w, (Rw * h) // w, torch.full_like(h, Rh))
+    top, left, flip = h_aug[:, 0], h_aug[:, 1], h_aug[:, 2]
+    if bool(((top < 0) | (top > nh - Rh) | (left < 0) | (left > nw - Rw)).any()):
+        raise ValueError('image_ingest_aug: a crop origin lies outside [0, nh - Rh] x [0, nw - Rw] of its resized image')
+    if bool(((flip != 0) & (flip != 1)).any()):
+        raise ValueError('image_ingest_aug: flip must be 0 or 1')
+    _lib.call('da_image_ingest_aug', raw.data_ptr(), off.data_ptr(), hw.data_ptr(), aug.data_ptr(), B, Rh, Rw,
+              out.data_ptr(), int(kind), _stream())
+
+
 def image_resize(raw, off, hw, Rh, Rw, out, kind, geometry, filter, range, host=None):
     """``image_ingest_rect`` with the transform as three switches (``da_image_resize``, the same kernel): ``geometry`` 0
     resize to cover + centre crop, 1 stretch each axis on its own; ``filter`` 0 the antialiased triangle filter (Pillow,

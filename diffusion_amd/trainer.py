@@ -131,7 +131,7 @@ class Trainer:
                  algorithms=None, eval_dataloader=None, eval_interval=None, device='gpu', run_name=None, seed=None,
                  scale_schedule_ratio: float = 1.0, save_folder=None, save_interval=None, save_overwrite=True,
                  autoresume=False, load_path=None, fsdp_config=None, precision=None, log_every: int = 10,
-                 use_graphs=False, eval_subset_num_batches=None, **unused):
+                 use_graphs=False, eval_subset_num_batches=None, max_graphs: int = 4, **unused):
         self.model = model
         self.dataloader = train_dataloader
         self.optimizer: FusedAdamW = optimizers
@@ -203,6 +203,10 @@ class Trainer:
             use_graphs = 'auto' if use_graphs.lower() == 'auto' else use_graphs.lower() in ('1', 'true', 'yes', 'on')
         self.use_graphs = use_graphs if use_graphs == 'auto' else bool(use_graphs)
         self._graph_cache = None
+        # captured graphs kept at a time (least recently replayed evicted first).  A run over aspect-ratio buckets sees one
+        # latent shape per bucket: with fewer slots than shapes in use it keeps re-capturing, with more each slot holds a
+        # microbatch's activations in a pool of its own
+        self.max_graphs = int(max_graphs)
         # resume: explicit load_path, or (autoresume) the newest checkpoint of this rank-0 run in save_folder
         self.all_algorithms = list(algorithms or [])
         self._skip_batches = 0
@@ -347,7 +351,7 @@ class Trainer:
             return False
         if self._graph_cache is None:
             from .graph_step import GraphStepCache
-            self._graph_cache = GraphStepCache(self.model)
+            self._graph_cache = GraphStepCache(self.model, self.max_graphs)
         if not self._graph_cache.usable(sub):
             return False
         if self.use_graphs is True:

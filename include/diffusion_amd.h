@@ -403,6 +403,17 @@ int da_image_ingest(const unsigned char* src, const long long* off, const int* h
  * misaligned out. */
 int da_image_ingest_rect(const unsigned char* src, const long long* off, const int* hw, int B, int Rh, int Rw, void* out,
                          int out_kind, da_stream_t stream);
+/* da_image_ingest_rect with the crop window and a horizontal flip chosen per image (random-crop / flip augmentation).  aug
+ * is a device table int32 [B][3] = (top, left, flip): the origins are in pixels of the resized (nh x nw) image,
+ * 0 <= top <= nh - Rh and 0 <= left <= nw - Rw, and out[Y][X] = resized[top + Y][c] with c = left + X for flip 0 and
+ * c = nw - 1 - (left + X) for flip 1, which is the crop at `left` of the horizontally mirrored image.  The kernel clamps
+ * both origins into range, so no table makes it read outside an image; an image whose flip is neither 0 nor 1 is skipped
+ * (nothing written for it), as one with a side above 65535 is.  The centre origins of da_image_ingest_rect with flip 0
+ * give its bits; flip 1 gives the bits of the mirrored source.  Resize rule, filter, arithmetic, outputs and argument
+ * rules are da_image_ingest_rect's.  DA_ERR_SHAPE (nothing launched) for a null aug and for everything
+ * da_image_ingest_rect rejects.  The table lives on the device: callers validate it on their host copy (ops.py does). */
+int da_image_ingest_aug(const unsigned char* src, const long long* off, const int* hw, const int* aug, int B, int Rh,
+                        int Rw, void* out, int out_kind, da_stream_t stream);
 /* The same kernel with the transform as three independent switches (every combination is valid); src, off, hw, out and
  * out_kind are da_image_ingest_rect's, and da_image_ingest_rect is this entry with (0, 0, 0).
  *   geometry 0: resize to cover Rh x Rw, then the centre crop;  1: stretch, each axis resized on its own to Rw and Rh;
