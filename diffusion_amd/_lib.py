@@ -61,6 +61,8 @@ SIGNATURES = {
     'da_timestep_embed_f32': [_fp, _vp, _i, _i, _vp],
     'da_add_noise': [_fp, _fp, _ll, _fp, _fp, _vp, _fp, _i, _i, _i, _vp],
     'da_add_noise_ex': [_fp, _fp, _vp, _i, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _vp],
+    'da_add_noise_rng': [_fp, _vp, _vp, _i, _vp, _i, _i, C.c_double, C.c_double, _fp, _fp, _i, _f, _f, _vp, _fp, _i, _i, _i,
+                         _i, _vp],
     'da_image_ingest': [_vp, _vp, _vp, _i, _i, _vp, _i, _vp],
     'da_image_ingest_rect': [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
     'da_image_ingest_aug': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],

@@ -51,4 +51,13 @@ __device__ __forceinline__ void normals(uint64_t seed, uint32_t pix, uint32_t dr
   pair(r[2], r[3], z[2], z[3]);
 }
 
+// v + k z with the product and the sum each rounded, never contracted into an FMA: how a draw is added wherever the result
+// is defined as the torch expression v + k * z (the two-step samplers' noise term, the training noise's offset and
+// perturbation terms)
+__device__ __forceinline__ float add_scaled_unfused(float v, float k, float z) {
+#pragma clang fp contract(off)
+  const float kz = k * z;
+  return v + kz;
+}
+
 }  // namespace philox

@@ -5,8 +5,11 @@
 // All use 16-B vector accesses along the contiguous (channel) axis and grid-stride loops.  GEGLU, SiLU, the two GELUs, add and
 // copy are instances of one kernel, map2d_kernel<Op, NIN, NOUT>, behind one launcher; the 4-channel latent loss runs the
 // general mse_partial_c_kernel at C = 4.
+#include <cmath>
+
 #include "common.hpp"
 #include "diffusion_amd.h"
+#include "philox.hpp"
 
 namespace {
 
@@ -184,6 +187,21 @@ __global__ void add_noise_kernel(const float* x0, const float* eps, const long l
   }
 }
 
+// ---- one channel of the general forward diffusion, shared by add_noise_ex_kernel and add_noise_rng_kernel: x_t = a x + s n_xt
+// and the target (0: the noise n_tg, 1: v = a n_tg - s x, 2: x).  Every product and every sum is rounded on its own: the
+// bits add_noise_ex_kernel has always had (its multiplies compile to packed ones, which never fused), now stated
+DEVINL void noise_channel(float a, float s, float x, float n_xt, float n_tg, int kind, float& v, float& tg) {
+#pragma clang fp contract(off)
+  const float ax = a * x, sn = s * n_xt;
+  v = ax + sn;
+  if (kind == 1) {
+    const float an = a * n_tg, sx = s * x;
+    tg = an - sx;
+  } else {
+    tg = kind == 2 ? x : n_tg;
+  }
+}
+
 // ---- general forward diffusion: C (1..8) channels, discrete (int64 t + sqrt(abar) tables) or continuous (fp32 angle t:
 // cos t x0 + sin t eps) noising; target eps, v or x0.  inputs NCHW fp32 [B,C,HW]; outputs NHWC-8 (pad channels = 0)
 template <bool CONT>
@@ -208,14 +226,121 @@ __global__ void add_noise_ex_kernel(const float* x0, const float* eps, const voi
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       if (c < C) {
-        float x = x0[(b * C + c) * HW + pix], n = eps[(b * C + c) * HW + pix];
-        o[c] = f2bf(a * x + s * n);
-        tg[c] = kind == 1 ? (a * n - s * x) : (kind == 2 ? x : n);
+        float x = x0[(b * C + c) * HW + pix], n = eps[(b * C + c) * HW + pix], v;
+        noise_channel(a, s, x, n, n, kind, v, tg[c]);
+        o[c] = f2bf(v);
       }
     }
     st8(xt + i * 8, o);
     *reinterpret_cast<f32x4*>(target + i * 8) = f32x4{tg[0], tg[1], tg[2], tg[3]};
     *reinterpret_cast<f32x4*>(target + i * 8 + 4) = f32x4{tg[4], tg[5], tg[6], tg[7]};
+  }
+}
+
+// ---- the same noising with every draw made in the launch (da_add_noise_rng): per sample b the key is seeds[b], the stream 0,
+// and the draw number says what a draw is for: 0 the noise n, 1 the perturbation z2, 2 the per-channel offset zc (pixel 0),
+// 3 the timestep (pixel 0, block 0, word r0).  A thread owns a pixel: it recomputes its sample's timestep and offset draws
+// (a few hundred integer and fp32 operations) and shares nothing with another thread, so nothing in the launch waits.
+struct NoiseRngArgs {
+  const float* x0;
+  const uint64_t* seeds;
+  const int* slot;  // NULL: plain uniform timesteps
+  void* t;          // written when draw_t, else read
+  const float *sqrt_ac, *sqrt_1mac;
+  bf16* xt;
+  float* target;
+  long total_pix;
+  long long t_lo, t_hi;  // discrete range
+  float tf_lo, tf_hi;    // continuous range
+  float noise_offset, perturbation;
+  int n_slots, draw_t, C, HW, kind;
+};
+// the slot of sample b, held inside [0, n_slots): a slot from device memory can never carry a timestep out of the table
+DEVINL uint32_t noise_slot(const NoiseRngArgs& p, long b) {
+  const int sl = p.slot[b];
+  return (uint32_t)(sl < 0 ? 0 : (sl >= p.n_slots ? p.n_slots - 1 : sl));
+}
+// t_lo + ((slot 2^32 + r0) R) / (n_slots 2^32): the division by 2^32 first (a shift), then a 32-bit one, which is the same
+// floor; the host admits n_slots R < 2^32 only, so the product stays below 2^64 and its upper half below 2^32
+DEVINL long long draw_timestep(const NoiseRngArgs& p, long b, uint32_t r0) {
+  const uint64_t R = (uint64_t)(p.t_hi - p.t_lo);
+  if (!p.slot) return p.t_lo + (long long)(((uint64_t)r0 * R) >> 32);
+  const uint64_t num = (((uint64_t)noise_slot(p, b) << 32) | r0) * R;
+  return p.t_lo + (long long)((uint32_t)(num >> 32) / (uint32_t)p.n_slots);
+}
+DEVINL float draw_time(const NoiseRngArgs& p, long b, uint32_t r0) {
+#pragma clang fp contract(off)
+  float u = (float)(r0 >> 8) * 0x1p-24f;
+  if (p.slot) {
+    const float su = (float)noise_slot(p, b) + u;
+    u = su / (float)p.n_slots;
+  }
+  const float span = p.tf_hi - p.tf_lo;
+  const float du = span * u;
+  return p.tf_lo + du;
+}
+template <bool CONT>
+__global__ void __launch_bounds__(PW_BLOCK) add_noise_rng_kernel(NoiseRngArgs p) {
+  const int C = p.C, HW = p.HW;
+  GRID_STRIDE(i, p.total_pix) {
+    const long b = i / HW;
+    const uint32_t pix = (uint32_t)(i - b * HW);
+    const uint64_t seed = p.seeds[b];
+    uint32_t r[4] = {0, 0, 0, 0};
+    if (p.draw_t) philox::words(0u, 3u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);  // uniform
+    float a, s;
+    if (CONT) {
+      float* tp = static_cast<float*>(p.t);
+      const float tt = p.draw_t ? draw_time(p, b, r[0]) : tp[b];
+      if (p.draw_t && pix == 0) tp[b] = tt;
+      a = cosf(tt);
+      s = sinf(tt);
+    } else {
+      long long* tp = static_cast<long long*>(p.t);
+      const long long tt = p.draw_t ? draw_timestep(p, b, r[0]) : tp[b];
+      if (p.draw_t && pix == 0) tp[b] = tt;
+      a = p.sqrt_ac[tt];
+      s = p.sqrt_1mac[tt];
+    }
+    float n1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n2[8];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (4 * k < C) philox::normals(seed, pix, 0u, 0u, (uint32_t)k, n1 + 4 * k);
+    if (p.noise_offset != 0.f) {  // uniform
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (4 * k < C) {
+          float zc[4];
+          philox::normals(seed, 0u, 2u, 0u, (uint32_t)k, zc);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) n1[4 * k + j] = philox::add_scaled_unfused(n1[4 * k + j], p.noise_offset, zc[j]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) n2[c] = n1[c];
+    if (p.perturbation != 0.f) {  // uniform
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (4 * k < C) {
+          float z2[4];
+          philox::normals(seed, pix, 1u, 0u, (uint32_t)k, z2);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) n2[4 * k + j] = philox::add_scaled_unfused(n1[4 * k + j], p.perturbation, z2[j]);
+        }
+    }
+    bf16x8 o = zero8();
+    float tg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        float v;
+        noise_channel(a, s, p.x0[(b * C + c) * HW + pix], n2[c], n1[c], p.kind, v, tg[c]);
+        o[c] = f2bf(v);
+      }
+    }
+    st8(p.xt + i * 8, o);
+    *reinterpret_cast<f32x4*>(p.target + i * 8) = f32x4{tg[0], tg[1], tg[2], tg[3]};
+    *reinterpret_cast<f32x4*>(p.target + i * 8 + 4) = f32x4{tg[4], tg[5], tg[6], tg[7]};
   }
 }
 
@@ -556,6 +681,44 @@ extern "C" int da_add_noise_ex(const float* x0, const float* eps, const void* t,
   else
     hipLaunchKernelGGL(add_noise_ex_kernel<false>, dim3(pw_blocks(total)), dim3(PW_BLOCK), 0, s, x0, eps, t, sqrt_ac,
                        sqrt_1mac, (bf16*)xt, target, C, HW, total, target_kind);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+extern "C" int da_add_noise_rng(const float* x0, const unsigned long long* seeds, const int* slot, int n_slots, void* t,
+                                int t_is_f32, int draw_t, double t_lo, double t_hi, const float* sqrt_ac,
+                                const float* sqrt_1mac, int T, float noise_offset, float perturbation, void* xt,
+                                float* target, int B, int C, int HW, int target_kind, hipStream_t s) {
+  DA_CLEAR_ERR();
+  if (B <= 0 || HW <= 0 || C < 1 || C > 8 || target_kind < 0 || target_kind > 2) return DA_ERR_SHAPE;
+  if (!x0 || !seeds || !t || !xt || !target) return DA_ERR_SHAPE;
+  if (((uintptr_t)seeds & 7) || ((uintptr_t)xt & 15) || ((uintptr_t)target & 15) || ((uintptr_t)x0 & 3) ||
+      ((uintptr_t)t & (t_is_f32 ? 3 : 7)) || ((uintptr_t)slot & 3))
+    return DA_ERR_SHAPE;
+  if (!t_is_f32 && (!sqrt_ac || !sqrt_1mac || T < 1)) return DA_ERR_SHAPE;
+  if (!std::isfinite(noise_offset) || !std::isfinite(perturbation)) return DA_ERR_SHAPE;
+  if (n_slots < 0 || (slot != nullptr) != (n_slots > 0)) return DA_ERR_SHAPE;
+  NoiseRngArgs p{};
+  if (draw_t) {
+    if (!(t_lo < t_hi) || !std::isfinite(t_lo) || !std::isfinite(t_hi)) return DA_ERR_SHAPE;
+    if (t_is_f32) {
+      // slot + u must be exact up to its one rounding: slots below 2^24
+      if ((double)(float)t_lo != t_lo || (double)(float)t_hi != t_hi || n_slots > (1 << 24)) return DA_ERR_SHAPE;
+      p.tf_lo = (float)t_lo, p.tf_hi = (float)t_hi;
+    } else {
+      if (t_lo != std::floor(t_lo) || t_hi != std::floor(t_hi) || t_lo < 0 || t_hi > (double)T) return DA_ERR_SHAPE;
+      p.t_lo = (long long)t_lo, p.t_hi = (long long)t_hi;
+      if ((uint64_t)n_slots * (uint64_t)(p.t_hi - p.t_lo) >= (1ull << 32)) return DA_ERR_SHAPE;
+    }
+  }
+  p.x0 = x0, p.seeds = reinterpret_cast<const uint64_t*>(seeds), p.slot = slot, p.t = t;
+  p.sqrt_ac = sqrt_ac, p.sqrt_1mac = sqrt_1mac, p.xt = (bf16*)xt, p.target = target;
+  p.total_pix = (long)B * HW;
+  p.noise_offset = noise_offset, p.perturbation = perturbation;
+  p.n_slots = n_slots, p.draw_t = draw_t ? 1 : 0, p.C = C, p.HW = HW, p.kind = target_kind;
+  if (t_is_f32)
+    hipLaunchKernelGGL(add_noise_rng_kernel<true>, dim3(pw_blocks(p.total_pix)), dim3(PW_BLOCK), 0, s, p);
+  else
+    hipLaunchKernelGGL(add_noise_rng_kernel<false>, dim3(pw_blocks(p.total_pix)), dim3(PW_BLOCK), 0, s, p);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

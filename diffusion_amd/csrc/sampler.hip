@@ -76,13 +76,9 @@ struct Rng {
 template <>
 struct Rng<false> {};  // the eight entries without it: the operand list and the code they always had
 
-// v + k z with the product and the sum each rounded: the two-step forms' noise term is defined as the torch expression
-// x += kn * z on the deterministic update, so it must not contract into an FMA
-__device__ __forceinline__ float add_scaled_unfused(float v, float k, float z) {
-#pragma clang fp contract(off)
-  const float kz = k * z;
-  return v + kz;
-}
+// v + k z with the product and the sum each rounded (philox.hpp): the two-step forms' noise term is defined as the torch
+// expression x += kn * z on the deterministic update, so it must not contract into an FMA
+using philox::add_scaled_unfused;
 
 // The step, every form of it.  First order (MS = false), coef = {cx, cm, cn, guidance} and, BLEND, {bA, bS, 0, 0} after it:
 //   m     = cfg ? pu + g (pt - pu) : p

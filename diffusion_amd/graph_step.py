@@ -11,7 +11,8 @@ flat buffer as in eager mode.
 
 What stays outside the graph: the RNG draws (timesteps, noise), metric updates, the optimizer step and the bucketed
 RCCL exchange (with more than one rank the LAST microbatch of a step runs eagerly so that the all-reduce of finished
-gradient buckets still overlaps its backward).
+gradient buckets still overlaps its backward).  A model in philox mode (train_noise.py) draws inside the captured noising
+launch: its graph owns static per-sample seeds (and strata) instead of the noise buffer, and a replay copies those.
 """
 from __future__ import annotations
 
@@ -25,7 +26,8 @@ from . import ops
 class GraphedMicrobatch:
     """Captured forward + loss + backward for one input signature."""
 
-    def __init__(self, model, latents: torch.Tensor, cond: torch.Tensor, weight: float):
+    def __init__(self, model, latents: torch.Tensor, cond: torch.Tensor, weight: float, n_slots: int = 0,
+                 injected_t: bool = False):
         unet = model.unet
         dev = unet.device_
         self.model = model
@@ -35,14 +37,28 @@ class GraphedMicrobatch:
         self.lat = torch.empty_like(latents, device=dev)
         self.cond = torch.empty_like(cond, device=dev)
         self.t = torch.zeros(self.B, device=dev, dtype=torch.int64)
-        self.noise = torch.empty(latents.shape, device=dev, dtype=torch.float32)
+        self.philox = getattr(model, 'train_noise', None) is not None and model.train_noise.philox
         self.lat.copy_(latents)
         self.cond.copy_(cond)
+        self.graph = torch.cuda.CUDAGraph()
+        if self.philox:
+            # the draws are part of the captured launch: what varies per replay is the per-sample seeds and, stratified, the
+            # samples' places among the n_slots of the global batch (n_slots itself is a launch argument, hence in the key);
+            # the kernel writes the timesteps, unless they are injected (self.t then feeds it)
+            self.seeds = torch.zeros(self.B, device=dev, dtype=torch.int64).view(torch.uint64)
+            self.slots = torch.zeros(self.B, device=dev, dtype=torch.int32)
+            self.n_slots, self.injected_t = int(n_slots), bool(injected_t)
+            self._capture()
+            return
+        self.noise = torch.empty(latents.shape, device=dev, dtype=torch.float32)
         # placeholder noise for the warm-up and the capture, from a generator of its own: a capture must not advance the global
         # stream the eager path draws from (a run over aspect-ratio buckets captures whenever a new shape turns up, and every
         # draw after it would differ from the eager run's)
         self.noise.normal_(generator=torch.Generator(device=dev).manual_seed(0))
-        self.graph = torch.cuda.CUDAGraph()
+        self._capture()
+
+    def _capture(self):
+        unet = self.model.unet
         # warm-up on a side stream (lazy one-time work - scratch buffers, split-K workspace, hipFuncSetAttribute, the
         # transposed-weight descriptor table - must not happen inside the capture); its gradient contribution is undone
         keep = unet.grad.clone()
@@ -66,9 +82,16 @@ class GraphedMicrobatch:
     def _body(self):
         model = self.model
         batch = {model.image_latents_key: self.lat, model.text_latents_key: self.cond}
-        out = model.forward(batch, timesteps=self.t, noise=self.noise)
+        if self.philox:
+            batch['_sample_seeds'] = self.seeds
+            if model.train_noise.stratified:
+                batch['_sample_slots'], batch['_n_slots'] = self.slots, self.n_slots
+            out = model.forward(batch, timesteps=self.t if self.injected_t else None)
+        else:
+            out = model.forward(batch, timesteps=self.t, noise=self.noise)
         loss = model.loss(out, batch, weight=self.weight)
         model.backward_from_loss()
+        self.t_out = out[2]
         return out[0], out[1], loss.detach()
 
     def replay(self, latents, cond, timesteps, noise):
@@ -78,6 +101,17 @@ class GraphedMicrobatch:
         self.noise.copy_(noise, non_blocking=True)
         self.graph.replay()
         return (self.pred, self.target, self.t), self.loss
+
+    def replay_philox(self, latents, cond, seeds, slots=None, timesteps=None):
+        self.lat.copy_(latents, non_blocking=True)
+        self.cond.copy_(cond, non_blocking=True)
+        self.seeds.view(torch.int64).copy_(seeds.view(torch.int64), non_blocking=True)   # the bits, whatever copy_ supports
+        if slots is not None:
+            self.slots.copy_(slots, non_blocking=True)
+        if timesteps is not None:
+            self.t.copy_(timesteps, non_blocking=True)
+        self.graph.replay()
+        return (self.pred, self.target, self.t_out), self.loss
 
 
 class GraphStepCache:
@@ -106,9 +140,12 @@ class GraphStepCache:
         m = self.model
         lat, cond = batch[m.image_latents_key], batch[m.text_latents_key]
         key = (tuple(lat.shape), lat.dtype, tuple(cond.shape), cond.dtype, round(float(weight), 9), m.prediction_type)
-        g = self.graphs.get(key)
         dev = m.unet.device_
         B = lat.shape[0]
+        tn = getattr(m, 'train_noise', None)
+        if tn is not None and tn.philox:
+            return self._step_philox(batch, weight, key, tn)
+        g = self.graphs.get(key)
         # the draws of stable_diffusion.py:177-179, from the same global generator as the eager path
         t = batch.get('_timesteps')
         if t is None:
@@ -116,11 +153,38 @@ class GraphStepCache:
         noise = batch.get('_noise')
         if noise is None:
             noise = torch.randn(lat.shape, device=dev, dtype=lat.dtype if lat.is_floating_point() else torch.float32)
+        return self._graph(key, lat, cond, weight).replay(lat, cond, t, noise)
+
+    def _graph(self, key, lat, cond, weight, **kw) -> GraphedMicrobatch:
+        """the captured microbatch of ``key``, captured now if there is none"""
+        g = self.graphs.get(key)
         if g is None:
             if len(self.graphs) >= self.max_graphs:
                 self.graphs.pop(next(iter(self.graphs)))   # the least recently replayed one
-            g = self.graphs[key] = GraphedMicrobatch(m, lat, cond, weight)
+            g = self.graphs[key] = GraphedMicrobatch(self.model, lat, cond, weight, **kw)
             self.captures += 1
         else:   # a bucketed run alternates shapes: keep the ones in use, evict by last use and not by age
             self.graphs[key] = self.graphs.pop(key)
-        return g.replay(lat, cond, t, noise)
+        return g
+
+    def _step_philox(self, batch, weight, key, tn):
+        """``step`` of a model in philox mode: the noising options, the number of strata and whether the timesteps are injected
+        are arguments of the captured launch, so they are part of the key; seeds absent from the batch come from torch's
+        generator, as in the eager ``forward``."""
+        from .train_noise import check_injected, generator_seeds
+        m = self.model
+        lat, cond = batch[m.image_latents_key], batch[m.text_latents_key]
+        dev, B = m.unet.device_, lat.shape[0]
+        check_injected(tn, batch.get('_noise'))
+        t = batch.get('_timesteps')
+        seeds = batch.get('_sample_seeds')
+        if seeds is None:
+            seeds = generator_seeds(B, dev)
+        slots, n_slots = None, 0
+        if tn.stratified:
+            slots, n_slots = batch.get('_sample_slots'), batch.get('_n_slots')
+            if slots is None:
+                slots, n_slots = torch.arange(B, dtype=torch.int32, device=dev), B
+        key = key + (tn.key(), int(n_slots), t is not None)
+        g = self._graph(key, lat, cond, weight, n_slots=int(n_slots), injected_t=t is not None)
+        return g.replay_philox(lat, cond, seeds, slots, t)

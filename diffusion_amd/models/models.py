@@ -25,6 +25,7 @@ from .composer_shim import MeanSquaredError
 from ..schedulers.schedulers import ContinuousTimeScheduler
 from .pixel_diffusion import PixelDiffusion
 from ..sampling import check_guidance_rescale
+from ..train_noise import TrainNoise
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
                          check_eta, check_inference_scheduler, check_snr_gamma, check_timestep_spacing,
                          make_inference_scheduler)
@@ -101,6 +102,13 @@ def _check_zero_snr_options(zero_terminal_snr, prediction_type, timestep_spacing
     return check_timestep_spacing(timestep_spacing)
 
 
+def _train_noise_options(noise_source, noise_offset, input_perturbation, timestep_range, timestep_sampling) -> TrainNoise:
+    """The factories' five noising keywords as ``TrainNoise`` (a YAML list becomes the range's tuple).  Host only."""
+    if isinstance(timestep_range, list):
+        timestep_range = tuple(timestep_range)
+    return TrainNoise(noise_source, noise_offset, input_perturbation, timestep_range, timestep_sampling)
+
+
 def _check_inference_eta(inference_eta, inference_scheduler) -> float:
     """``inference_eta=`` of the factories: a number in [0, 1], and 0 unless the solver is DDIM.  Host only."""
     inference_eta = check_eta(inference_eta)
@@ -132,6 +140,11 @@ def stable_diffusion_2(
     inference_eta: float = 0.0,
     lora_path: Optional[str] = None,
     lora_scale: float = 1.0,
+    noise_source: str = 'torch',
+    noise_offset: float = 0.0,
+    input_perturbation: float = 0.0,
+    timestep_range=None,
+    timestep_sampling: str = 'uniform',
 ):
     """``lora_path``: a safetensors LoRA file (diffusion_amd/lora.py) attached to the U-Net at ``lora_scale`` times its own
     alpha / r; sampling and evaluation then run with the adapted weights (``model.unload_lora()`` restores the base).
@@ -146,7 +159,13 @@ def stable_diffusion_2(
     arXiv:2305.08891; ``rescale_betas_zero_snr``); needs a v-prediction U-Net config.  ``timestep_spacing``: the inference
     grid, ``'leading'`` or ``'trailing'``; None means ``'trailing'`` with ``zero_terminal_snr``, else ``'leading'``.
     ``guidance_rescale``: the model's default for ``generate()``.  ``snr_gamma``: Min-SNR-gamma loss weighting
-    (``StableDiffusion``).  What any of them does to image quality with trained weights has not been measured here."""
+    (``StableDiffusion``).  What any of them does to image quality with trained weights has not been measured here.
+
+    ``noise_source``, ``noise_offset``, ``input_perturbation``, ``timestep_range``, ``timestep_sampling``: the noising of the
+    training step (``train_noise.TrainNoise``).  ``'philox'`` draws timesteps and noise per sample inside the noising launch,
+    independent of the microbatch split and the world size; the other four need it."""
+    train_noise = _train_noise_options(noise_source, noise_offset, input_perturbation, timestep_range, timestep_sampling)
+    train_noise.discrete_range(1000)
     check_inference_scheduler(inference_scheduler)
     inference_eta = _check_inference_eta(inference_eta, inference_scheduler)
     pt = _resolve_unet_config(model_name, unet_config, probe=True).prediction_type
@@ -236,6 +255,7 @@ def stable_diffusion_2(
         fsdp=fsdp,
         snr_gamma=snr_gamma,
         guidance_rescale=guidance_rescale,
+        train_noise=train_noise,
     )
     model.vae_hip = vae_hip if build_encoders else None
     model.vae_dec_hip = vae_dec_hip if build_encoders else None
@@ -269,10 +289,14 @@ def _pixel_unet(unet_config: Optional[UNetConfig], seed: int) -> UNetHIP:
 
 def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
                              unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler: str = 'ddim',
-                             inference_eta: float = 0.0):
+                             inference_eta: float = 0.0, noise_source: str = 'torch', noise_offset: float = 0.0,
+                             input_perturbation: float = 0.0, timestep_range=None, timestep_sampling: str = 'uniform'):
     """Discrete-time (DDPM, 1000 steps) pixel diffusion; DDIM for inference (reference models.py:115-172), or with
     ``inference_scheduler='dpm++2m'`` the second-order multistep solver (``DPMSolverMultistepScheduler``), with
-    ``'dpm++2m-sde'`` its SDE form.  ``inference_eta``: the DDIM sampler's eta in [0, 1] (0: deterministic)."""
+    ``'dpm++2m-sde'`` its SDE form.  ``inference_eta``: the DDIM sampler's eta in [0, 1] (0: deterministic).  The five
+    noising keywords are ``stable_diffusion_2``'s (``train_noise.TrainNoise``)."""
+    train_noise = _train_noise_options(noise_source, noise_offset, input_perturbation, timestep_range, timestep_sampling)
+    train_noise.discrete_range(1000)
     check_inference_scheduler(inference_scheduler)
     inference_eta = _check_inference_eta(inference_eta, inference_scheduler)
     if not torch.cuda.is_available():
@@ -288,18 +312,23 @@ def discrete_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch
         inference_scheduler.eta = inference_eta
     model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
                            prediction_type=prediction_type, train_metrics=[MeanSquaredError()],
-                           val_metrics=[MeanSquaredError()])
+                           val_metrics=[MeanSquaredError()], train_noise=train_noise)
     model.text_hip = text_hip
     return model
 
 
 def continuous_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-patch14', prediction_type='epsilon',
                                use_ode=False, train_t_max=1.570795, inference_t_max=1.56,
-                               unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler=None):
+                               unet_config: Optional[UNetConfig] = None, seed: int = 17, inference_scheduler=None,
+                               noise_source: str = 'torch', noise_offset: float = 0.0, input_perturbation: float = 0.0,
+                               timestep_range=None, timestep_sampling: str = 'uniform'):
     """Continuous-time pixel diffusion: the VP process with angle = time (tangent schedule), t in [0, train_t_max) for
     training, the reverse SDE (or with ``use_ode`` the probability-flow ODE) from ``inference_t_max`` for generation
     (reference models.py:175-228).  ``inference_scheduler`` exists to refuse: the named solvers (``'ddim'``,
-    ``'dpm++2m'``) and multistep scheduler objects are discrete-time methods and raise ``ValueError``."""
+    ``'dpm++2m'``) and multistep scheduler objects are discrete-time methods and raise ``ValueError``.  The five noising
+    keywords are ``stable_diffusion_2``'s; ``timestep_range`` is in fractions of ``train_t_max``."""
+    train_noise = _train_noise_options(noise_source, noise_offset, input_perturbation, timestep_range, timestep_sampling)
+    train_noise.continuous_range(train_t_max)
     check_inference_scheduler(inference_scheduler, continuous_time=True)
     if inference_scheduler is not None:
         raise ValueError('continuous_pixel_diffusion builds its own ContinuousTimeScheduler (use_ode, inference_t_max)')
@@ -312,6 +341,6 @@ def continuous_pixel_diffusion(clip_model_name: str = 'openai/clip-vit-large-pat
                                                   use_ode=use_ode)
     model = PixelDiffusion(unet, text_encoder, tokenizer, noise_scheduler, inference_scheduler=inference_scheduler,
                            prediction_type=prediction_type, continuous_time=True, train_metrics=[MeanSquaredError()],
-                           val_metrics=[MeanSquaredError()])
+                           val_metrics=[MeanSquaredError()], train_noise=train_noise)
     model.text_hip = text_hip
     return model

@@ -19,6 +19,8 @@ import torch
 
 from .. import ops
 from ..sampling import LatentSampler, check_seed, image_seeds, philox_latents, resolve_sampler
+from ..train_noise import TrainNoise, check_injected
+from ..train_noise import add_noise as train_noise_add
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
 from .schedulers import check_eta, check_inference_scheduler, is_stochastic, resolve_inference_scheduler, with_eta
 from .stable_diffusion import (_HIPBackward, _check_prompt_given, _check_prompt_lenths, _philox_step_noise, _prompt_batch,
@@ -42,8 +44,17 @@ class PixelDiffusion(ComposerModel):
                  prediction_type: str = 'epsilon',
                  train_metrics: Optional[List] = None,
                  val_metrics: Optional[List] = None,
-                 val_seed: int = 1138):
+                 val_seed: int = 1138,
+                 train_noise: Optional[TrainNoise] = None):
         super().__init__()
+        # the noising options (train_noise.TrainNoise): with noise_source='philox' forward draws per sample in the noising
+        # launch; a range outside the schedule is refused here
+        self.train_noise = train_noise if train_noise is not None else TrainNoise()
+        if self.train_noise.timestep_range is not None:
+            if continuous_time:
+                self.train_noise.continuous_range(scheduler.t_max)
+            else:
+                self.train_noise.discrete_range(len(scheduler))
         self.model = model
         self.text_encoder = text_encoder
         self.tokenizer = tokenizer
@@ -83,17 +94,28 @@ class PixelDiffusion(ComposerModel):
                 noise: Optional[torch.Tensor] = None):
         """Returns ``(model_out, targets, timesteps)`` like the reference (:96).  ``t`` is ``t_max * rand`` (continuous) or
         ``randint(0, len(scheduler))`` (discrete) from ``generator``; the noise from torch's global generator (:76-82).
-        ``timesteps`` / ``noise`` may be injected (as arguments or as ``batch['_timesteps']`` / ``batch['_noise']``)."""
+        ``timesteps`` / ``noise`` may be injected (as arguments or as ``batch['_timesteps']`` / ``batch['_noise']``).
+        With ``train_noise.noise_source == 'philox'`` the noising launch draws both per sample from
+        ``batch['_sample_seeds']`` (else from seeds drawn with ``generator``), as in ``StableDiffusion.forward``."""
         if timesteps is None:
             timesteps = batch.get('_timesteps')
         if noise is None:
             noise = batch.get('_noise')
+        check_injected(self.train_noise, noise)
         unet: UNetHIP = self.model
         dev = unet.device_
         inputs = batch[self.input_key].to(dev)
         conditioning = self._text_states(batch[self.conditioning_key])
         B, C, H, W = inputs.shape
         unet.check_spatial(H, W)
+        if self.train_noise.philox:   # one launch draws and noises, per sample (StableDiffusion.forward has the details)
+            sched = dict(t_max=self.scheduler.t_max) if self.continuous_time else dict(tables=self.scheduler.device_tables(dev))
+            xt, target8, t = train_noise_add(self.train_noise, batch, inputs.float().contiguous(), timesteps,
+                                             self.prediction_type, generator=generator, **sched)
+            pred8 = unet.forward_features(xt, t, unet.prepare_ctx(conditioning), B, (H, W))
+            self._pending = (pred8, target8, B * H * W, C)
+            return (pred8.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2),
+                    target8.view(B, H, W, 8)[..., :C].permute(0, 3, 1, 2), t)
         if timesteps is None:
             if self.continuous_time:
                 timesteps = self.scheduler.t_max * torch.rand(B, device=dev, generator=generator)

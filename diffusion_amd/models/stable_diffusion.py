@@ -21,6 +21,8 @@ import torch.nn.functional as F
 from .. import ops
 from ..sampling import (LatentSampler, check_guidance_rescale, check_seed, image_seeds, philox_latents, rescale_noise_cfg,
                         resolve_sampler)
+from ..train_noise import TrainNoise, check_injected
+from ..train_noise import add_noise as train_noise_add
 from .composer_shim import ComposerModel, MeanSquaredError, Metric
 from .schedulers import (check_eta, check_inference_scheduler, check_snr_gamma, check_timestep_spacing,
                          check_zero_snr_grid, is_stochastic, min_snr_weights, resolve_inference_scheduler, with_eta,
@@ -72,12 +74,18 @@ class StableDiffusion(ComposerModel):
                  fsdp: bool = False,
                  prediction_type: Optional[str] = None,
                  snr_gamma: Optional[float] = None,
-                 guidance_rescale: float = 0.0):
+                 guidance_rescale: float = 0.0,
+                 train_noise: Optional[TrainNoise] = None):
         """``snr_gamma``: None, or the gamma of Min-SNR loss weighting (Hang et al., arXiv:2303.09556): every sample's
         squared error and gradient are weighted by its timestep's entry of ``schedulers.min_snr_weights`` in the fused loss
         launch (``ops.mse_loss_w``); ``loss()`` then reports the weighted loss.  ``guidance_rescale``: the default of
-        ``generate(guidance_rescale=None)``, hence of ``eval_forward`` and the image metrics and loggers built on it."""
+        ``generate(guidance_rescale=None)``, hence of ``eval_forward`` and the image metrics and loggers built on it.
+        ``train_noise``: the noising options (``train_noise.TrainNoise``); with ``noise_source='philox'`` ``forward`` draws
+        timesteps and noise per sample inside the noising launch."""
         super().__init__()
+        self.train_noise = train_noise if train_noise is not None else TrainNoise()
+        if self.train_noise.timestep_range is not None:   # an out-of-table range is refused here, not at the first step
+            self.train_noise.discrete_range(len(noise_scheduler))
         self.snr_gamma = _check_loss_options(snr_gamma, loss_fn)
         self.guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._snr_tables = {}
@@ -214,17 +222,34 @@ class StableDiffusion(ComposerModel):
     def forward(self, batch, timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None):
         """Returns ``(unet_out, target, timesteps)`` like the reference (:183).  ``timesteps`` / ``noise`` may be
         injected for parity tests (as arguments, or as ``batch['_timesteps']`` / ``batch['_noise']`` so that they pass
-        through a trainer's microbatch slicing); by default they are drawn from torch's global RNG exactly as :177-179."""
+        through a trainer's microbatch slicing); by default they are drawn from torch's global RNG exactly as :177-179.
+
+        With ``train_noise.noise_source == 'philox'`` the noising launch draws them per sample (``ops.add_noise_rng``) from
+        ``batch['_sample_seeds']`` (uint64 [B]; without it B seeds are drawn from torch's generator on the device) and, for
+        stratified timesteps, ``batch['_sample_slots']`` / ``batch['_n_slots']``; ``target`` is then a view of the kernel's
+        NHWC-8 target for either prediction type, injected timesteps are read, and injected noise is a ``ValueError``."""
         if timesteps is None:
             timesteps = batch.get('_timesteps')
         if noise is None:
             noise = batch.get('_noise')
+        check_injected(self.train_noise, noise)
         latents, conditioning = self._encode(batch)
         unet: UNetHIP = self.unet
         dev = unet.device_
         latents = latents.to(dev)
         B, _, H, W = latents.shape
         unet.check_spatial(H, W)
+        if self.train_noise.philox:
+            # one launch draws and noises: seeds (and strata) per sample from the batch, no NCHW noise tensor; the kernel
+            # leaves the timesteps in device memory for the embedding and the Min-SNR weights
+            xt, target8, t = train_noise_add(self.train_noise, batch, latents.float().contiguous(), timesteps,
+                                             self.prediction_type, self.noise_scheduler.device_tables(dev))
+            ctx = unet.prepare_ctx(conditioning.to(dev))
+            pred8 = unet.forward_features(xt, t, ctx, B, (H, W))
+            self._pending = (pred8, target8, B * H * W)
+            self._pending_t = t if self.snr_gamma is not None else None
+            return (pred8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2),
+                    target8.view(B, H, W, 8)[..., :4].permute(0, 3, 1, 2), t)
         if timesteps is None:
             timesteps = torch.randint(0, len(self.noise_scheduler), (B,), device=dev)
         if noise is None:

@@ -7,7 +7,10 @@ passed as ld, so column slices of wider buffers (fused QKV, concat buffers) are 
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 import os
+import struct
 from typing import Optional, Tuple
 
 import torch
@@ -527,6 +530,72 @@ def add_noise_ex(x0, eps, t, xt, target, prediction_type='epsilon', sqrt_ac=None
     else:
         raise ValueError(f'add_noise_ex: t must be int64 (discrete) or fp32 (continuous), got {t.dtype}')
     _lib.call('da_add_noise_ex', x0.data_ptr(), eps.data_ptr(), t.data_ptr(), is_f32, pa, pb, xt.data_ptr(),
+              target.data_ptr(), B, C, HW, NOISE_TARGETS[prediction_type], _stream())
+
+
+def add_noise_rng(x0, seeds, t, xt, target, prediction_type='epsilon', sqrt_ac=None, sqrt_1mac=None, *, draw_t=True,
+                  t_range=None, slots=None, n_slots=0, noise_offset=0.0, perturbation=0.0):
+    """The noising of ``add_noise_ex`` with every draw made in the launch (``da_add_noise_rng``): no noise tensor, sample
+    b's noise, offset, perturbation and timestep come from its own Philox key ``seeds[b]`` (uint64 [B] on the device).
+    ``t`` int64 [B] (discrete, with both tables) or fp32 [B] (continuous) on the device: written with the drawn timesteps
+    when ``draw_t``, else read.  ``t_range`` = (lo, hi): integers inside the table (default all of it), or fp32 values for
+    continuous time (required).  ``slots`` int32 [B] on the device with ``n_slots``: timesteps stratified over n_slots."""
+    if x0.dim() != 4:
+        raise ValueError('add_noise_rng: x0 must be [B,C,H,W]')
+    B, C = x0.shape[0], x0.shape[1]
+    HW = x0.shape[2] * x0.shape[3]
+    if x0.dtype != F32 or not x0.is_cuda or not x0.is_contiguous() or B < 1 or HW < 1 or HW > 2**31 - 1:
+        raise ValueError('add_noise_rng: x0 must be a contiguous fp32 [B,C,H,W] device tensor with H W in 1..2^31 - 1')
+    if not 1 <= C <= 8:
+        raise ValueError(f'add_noise_rng: {C} channels (1..8 supported)')
+    for z, dt in ((xt, BF16), (target, F32)):
+        if z.dtype != dt or not z.is_cuda or not z.is_contiguous() or z.numel() != B * HW * 8 or z.data_ptr() % 16:
+            raise ValueError('add_noise_rng: xt bf16 [B*HW,8], target fp32 [B*HW,8], contiguous on device')
+    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.uint64 or not seeds.is_cuda or not seeds.is_contiguous() \
+            or tuple(seeds.shape) != (B,) or seeds.data_ptr() % 8:
+        raise ValueError(f'add_noise_rng: seeds must be a contiguous uint64 [{B}] device tensor')
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+        raise ValueError('add_noise_rng: t must be a contiguous [B] device tensor')
+    if prediction_type not in NOISE_TARGETS:
+        raise ValueError(f'add_noise_rng: unknown prediction_type {prediction_type!r}')
+    noise_offset, perturbation = float(noise_offset), float(perturbation)
+    if not math.isfinite(noise_offset) or not math.isfinite(perturbation):
+        raise ValueError(f'add_noise_rng: noise_offset = {noise_offset}, perturbation = {perturbation} must be finite')
+    if t.dtype == F32:
+        is_f32, pa, pb, T = 1, None, None, 0
+    elif t.dtype == torch.int64:
+        if sqrt_ac is None or sqrt_1mac is None or int(sqrt_ac.numel()) != int(sqrt_1mac.numel()) or sqrt_ac.numel() < 1:
+            raise ValueError('add_noise_rng: discrete t needs both sqrt(abar) tables')
+        T = int(sqrt_ac.numel())
+        is_f32, pa, pb = 0, _vec(sqrt_ac, T, 'sqrt_ac'), _vec(sqrt_1mac, T, 'sqrt_1mac')
+    else:
+        raise ValueError(f'add_noise_rng: t must be int64 (discrete) or fp32 (continuous), got {t.dtype}')
+    n_slots = int(n_slots)
+    if n_slots < 0 or (slots is None) != (n_slots == 0):
+        raise ValueError(f'add_noise_rng: slots and n_slots >= 1 go together (n_slots = {n_slots})')
+    if slots is not None and (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda
+                              or not slots.is_contiguous() or tuple(slots.shape) != (B,)):
+        raise ValueError(f'add_noise_rng: slots must be a contiguous int32 [{B}] device tensor')
+    lo = hi = 0.0
+    if draw_t:
+        if t_range is None:
+            if is_f32:
+                raise ValueError('add_noise_rng: continuous time needs t_range = (lo, hi)')
+            t_range = (0, T)
+        lo, hi = t_range
+        if is_f32:
+            lo, hi = float(lo), float(hi)
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi) or n_slots > 2**24 \
+                    or any(struct.unpack('f', struct.pack('f', v))[0] != v for v in (lo, hi)):
+                raise ValueError(f'add_noise_rng: t_range = ({lo}, {hi}) must be fp32 values with lo < hi; n_slots <= 2^24')
+        else:
+            if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in (lo, hi)) or not 0 <= lo < hi <= T:
+                raise ValueError(f'add_noise_rng: t_range = ({lo}, {hi}) must be integers with 0 <= lo < hi <= {T}')
+            if n_slots * (hi - lo) >= 2**32:
+                raise ValueError(f'add_noise_rng: n_slots * (hi - lo) = {n_slots * (hi - lo)} must stay below 2^32')
+            lo, hi = float(lo), float(hi)
+    _lib.call('da_add_noise_rng', x0.data_ptr(), seeds.data_ptr(), None if slots is None else slots.data_ptr(), n_slots,
+              t.data_ptr(), is_f32, 1 if draw_t else 0, lo, hi, pa, pb, T, noise_offset, perturbation, xt.data_ptr(),
               target.data_ptr(), B, C, HW, NOISE_TARGETS[prediction_type], _stream())
 
 

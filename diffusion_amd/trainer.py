@@ -150,6 +150,9 @@ class Trainer:
         self.save_folder = save_folder
         self.save_interval = _parse_time(save_interval)[0] if save_interval else None
         self.batch_idx = 0
+        # the key of the per-sample noise seeds of a model in philox mode (train_noise.sample_seeds): the run's ``seed``, else
+        # the seed torch's generator was given; it travels in the checkpoints
+        self.seed = (int(seed) if seed is not None else torch.initial_seed()) & (2**64 - 1)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.reducer = BucketedAllReducer(model.unet.grad)
@@ -271,6 +274,12 @@ class Trainer:
         model, unet = self.model, self.model.unet
         n = next(v.shape[0] for v in batch.values() if torch.is_tensor(v))
         self.global_batch_size = n * self.world
+        tn = getattr(model, 'train_noise', None)
+        if tn is not None and tn.philox and '_sample_seeds' not in batch:
+            # seeds and strata by the sample's place in the GLOBAL batch, attached before the batch is sliced: the microbatch
+            # size and the world size drop out of what a sample is trained on, and a resumed run needs batch_idx only
+            from .train_noise import batch_entries
+            batch = dict(batch, **batch_entries(self.seed, self.batch_idx, self.rank, self.world, n, unet.device_))
         mb = self.microbatch
         if mb is None:
             if hasattr(model, 'unet_input_side'):   # the model knows its U-Net input (pixel models: no VAE, no /8)
@@ -418,6 +427,12 @@ class Trainer:
             if 'image_raw' in batch:
                 batch = model.ingest_raw(batch)
             batch = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
+            tn = getattr(model, 'train_noise', None)
+            if tn is not None and tn.philox and '_sample_seeds' not in batch:
+                # the same draws at every evaluation: the validation MSE of unchanged weights is one number
+                from .train_noise import batch_entries
+                nb = next(v.shape[0] for v in batch.values() if torch.is_tensor(v))
+                batch.update(batch_entries(getattr(model, 'val_seed', 0), i, self.rank, self.world, nb, dev))
             outputs = model.eval_forward(batch)
             for m in metrics.values():
                 model.update_metric(batch, outputs, m)
@@ -450,7 +465,7 @@ class Trainer:
         tmp = path + '.tmp'
         torch.save({'state': {'model': {f'unet.{k}': v.detach().cpu().contiguous() for k, v in unet.state_dict().items()},
                               'optimizers': self.optimizer.state_dict(), 'algorithms': algs, 'batch': self.batch_idx,
-                              'rng': rng, 'world': self.world}}, tmp)
+                              'rng': rng, 'world': self.world, 'noise_seed': self.seed}}, tmp)
         os.replace(tmp, path)   # a killed run never leaves a half-written newest checkpoint for autoresume
 
     @staticmethod
@@ -474,6 +489,7 @@ class Trainer:
             if type(a).__name__ in algs and hasattr(a, 'load_state_dict'):
                 a.load_state_dict(algs[type(a).__name__])
         self.batch_idx = ck['state']['batch']
+        self.seed = ck['state'].get('noise_seed', self.seed)
         rng = ck['state'].get('rng')
         if rng is not None:
             if self.rank == 0 and ck['state'].get('world', 1) == self.world:

@@ -350,6 +350,42 @@ int da_sampler_step_ms_blend_rs(const float* pred, const float* x, float* hist, 
  * 1..8, stream outside {0, 1}, kind outside {0, 1}, kind 1 with C % 4, a NULL or misaligned pointer. */
 int da_randn_philox(const unsigned long long* seeds, unsigned draw, unsigned stream, float* out, int B, int C, int H, int W,
                     int kind, da_stream_t hip_stream);
+/* The training step's noising with every draw made inside the launch: da_add_noise_ex without a noise operand.  x0 fp32
+ * NCHW [B][C][HW], C = 1..8; xt bf16 [B HW][8] and target fp32 [B HW][8] laid out as da_add_noise_ex lays them out, channels
+ * C..7 exactly +0; t int64 [B] (t_is_f32 = 0, with the tables sqrt_ac / sqrt_1mac of T entries) or fp32 [B] angles
+ * (t_is_f32 = 1, tables not read), in DEVICE memory: written with the drawn timesteps when draw_t, else read and left as it is.
+ * Per sample b the key is seeds[b] (DEVICE uint64 [B], 8-byte aligned) and the stream 0 of da_randn_philox; the draw number
+ * says what a draw is for:
+ *   draw 0  counter (pix, 0, 0, c / 4)   n,  the noise: the bits of da_randn_philox(seeds, 0, 0, [B, C, H, W])
+ *   draw 1  counter (pix, 1, 0, c / 4)   z2, the perturbation draw, made iff perturbation != 0
+ *   draw 2  counter (0, 2, 0, c / 4)     zc, one normal per (sample, channel), made iff noise_offset != 0: the bits of
+ *                                        da_randn_philox(seeds, 2, 0, [B, C, 1, 1])
+ *   draw 3  counter (0, 3, 0, 0)         word r0: the timestep, made iff draw_t
+ * Each product and each sum below is rounded once (no FMA):
+ *   n1 = n  + noise_offset zc[c]         the target's noise  (diffusers --noise_offset: noise += offset randn(B, C, 1, 1))
+ *   n2 = n1 + perturbation z2            the noise of x_t only  (Ning et al., arXiv:2301.11706; diffusers --input_perturbation)
+ *   x_t    = what da_add_noise_ex gives for (x0, eps = n2, t);   target = what it gives for (x0, eps = n1, t)
+ * so with both options 0 the launch gives the bits of da_add_noise_ex fed da_randn_philox's draw 0.
+ * Timesteps (draw_t): slot NULL and n_slots 0 draw uniformly; else slot is DEVICE int32 [B], the sample's stratum among
+ * n_slots (values outside [0, n_slots) are clamped into it).
+ *   discrete, integers 0 <= t_lo < t_hi <= T, R = t_hi - t_lo:
+ *     uniform      t = t_lo + ((uint64) r0 R >> 32)
+ *     stratified   t = t_lo + ((slot 2^32 + r0) R) / (n_slots 2^32)      in uint64; needs n_slots R < 2^32
+ *   continuous, t_lo < t_hi both fp32 values, u = (r0 >> 8) 2^-24, every operation rounded to fp32:
+ *     uniform      t = t_lo + (t_hi - t_lo) u
+ *     stratified   the same with u' = (slot + u) / n_slots              n_slots <= 2^24
+ * Both integer forms land in [t_lo, t_hi), the stratified one in [t_lo + floor(slot R / n_slots), t_lo + ceil((slot + 1) R /
+ * n_slots)).  The timestep of sample b is written by the one thread that owns its pixel 0; no thread reads what another wrote,
+ * and the launch allocates nothing and synchronises nothing: it may sit in a captured graph.  Without draw_t the range, slot and
+ * n_slots are not used.  DA_ERR_SHAPE, with nothing written, for C outside 1..8, an unknown target_kind, B or HW <= 0,
+ * (draw_t) t_lo >= t_hi, a discrete range that is fractional or outside [0, T], a continuous bound that is no fp32 value,
+ * n_slots < 0, slot without n_slots or the reverse, n_slots R >= 2^32 (discrete) or n_slots > 2^24 (continuous), a NULL x0 /
+ * seeds / t / xt / target, a misaligned pointer (seeds 8 bytes; xt, target 16), missing tables or T < 1 with t_is_f32 = 0,
+ * a noise_offset or perturbation that is not finite. */
+int da_add_noise_rng(const float* x0, const unsigned long long* seeds, const int* slot, int n_slots, void* t, int t_is_f32,
+                     int draw_t, double t_lo, double t_hi, const float* sqrt_ac, const float* sqrt_1mac, int T,
+                     float noise_offset, float perturbation, void* xt, float* target, int B, int C, int HW, int target_kind,
+                     da_stream_t stream);
 /* The stochastic step: any of the eight forms above with the noise term drawn inside the kernel.  `form` is a mask:
  * 1 two-step (hist), 2 blended (known8 / eps8 / mask), 4 rescaled (factor); the operands of a form that is not selected are
  * not read and may be NULL.  seeds: DEVICE uint64 [npix / HW], 8-byte aligned, required; HW is the pixel count of one
